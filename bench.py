@@ -23,6 +23,15 @@ and the scaling is "strong".  Rank 0 prints one JSON line.
 --exchange allgather selects the whole-matrix all-gather instead.
 --backend gloo: the N-rank rehearsal on one GPU (collectives staged through
 the host; every rank on cuda:(local_rank mod device count)).
+
+A plain run sets up, warms up, times --steps rounds and prints the headline
+line (metric, value, ms_per_step, the configuration).  --dump-outputs DIR
+also writes what the last timed round computed as DIR/<name>.npy.  --full
+adds the diagnostics, each a run of its own after the timed rounds:
+aggregate-ms of every aggregator, the distance-phase and Gram rooflines, the
+training-phase time, the MFMA utilisation from the committed profiles, the
+global model's sha256 against the reference run, and the CPU baseline
+(--no-cpu-baseline skips it).
 """
 from __future__ import annotations
 
@@ -418,6 +427,37 @@ def needs_launch(gpus: int, env=None) -> bool:
     return False
 
 
+DUMP_MODEL_MAX = 12 << 20  # float32 coordinates of the global model in a dump (48 MiB)
+
+
+def dump_outputs(eng, krum: bool, path: str) -> None:
+    """What the last run_round() handed its caller, as path/<name>.npy: the
+    global model it returned (global_model, float32 [P], 47 MB at C3), this
+    rank's clients' last local-step losses (client_losses, float32) and, for
+    the Krum family, the distance matrix, the scores and the clients in
+    selection order (krum_distances, krum_scores, krum_order; float64).
+    Inputs and initial weights are seeded, so two builds can be compared
+    array for array.  A model above DUMP_MODEL_MAX coordinates (C4 / C5) is
+    written as that many of them, drawn without replacement by a generator
+    of seed 0 and sorted — the same coordinates in every run; everything
+    else is small, so a dump stays below 64 MB."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    glob = eng.global_flat.detach().cpu().numpy().astype(np.float32, copy=False)
+    if glob.size > DUMP_MODEL_MAX:
+        glob = glob[np.sort(np.random.default_rng(0).choice(glob.size, DUMP_MODEL_MAX, replace=False))]
+    arrays = {"global_model": glob}
+    if eng.losses is not None:
+        arrays["client_losses"] = eng.losses.detach().cpu().numpy().astype(np.float32, copy=False)
+    if krum:
+        for name, t in (("krum_distances", eng.defense.distances), ("krum_scores", eng.defense.scores_device),
+                        ("krum_order", eng.defense.order_device)):
+            if t is not None:
+                arrays[name] = t.detach().cpu().numpy().astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def _free_port() -> int:
     import socket
     s = socket.socket()
@@ -427,7 +467,7 @@ def _free_port() -> int:
     return port
 
 
-def main() -> None:
+def arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -438,7 +478,13 @@ def main() -> None:
                     help="BASELINE.json config preset (C3 = the headline metric's workload)")
     ap.add_argument("--clients", type=int, default=None)
     ap.add_argument("--local-steps", type=int, default=5)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed rounds also run the diagnostics: aggregate-ms of every aggregator, the "
+                         "distance-phase and Gram rooflines, the training-phase time, the profile-derived MFMA "
+                         "utilisation, the global model's sha256 against the reference run, the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed round computed as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--exchange", default="auto", choices=["auto", "alltoall", "allgather"])
     ap.add_argument("--pairwise", default="reference", choices=["gram", "reference"],
@@ -452,7 +498,11 @@ def main() -> None:
     ap.add_argument("--kernel-stats", default=None,
                     help="rocprofv3 kernel_stats.csv (or the committed text summary) of THIS code's C3 bench, "
                          "for conv_mfma_from_profile (default: the newest committed profiles/*c3_kernel_stats*)")
-    args = ap.parse_args()
+    return ap
+
+
+def main() -> None:
+    args = arg_parser().parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     if needs_launch(args.gpus):
@@ -515,11 +565,53 @@ def main() -> None:
     torch.cuda.synchronize()
     fdist.barrier()
     elapsed = fdist.max_over_ranks(time.perf_counter() - t0, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, krum, args.dump_outputs)
 
-    # ---- untimed diagnostics after the timed region ----
+    sharded = eng.exchange == "alltoall"
+    out = {
+        "metric": METRIC,
+        "value": args.steps / elapsed,
+        "unit": "rounds/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "strong",
+        "vs_baseline": None,
+        "dtype": "f32 (bf16x6-split MFMA conv/GEMM = fp32 operands; Krum Gram bf16x4 hi/lo split, fp32 accumulate)",
+        "data": "synthetic (SURVEY §8d: N(0,1) 3x32x32 images, U{0..999} 16-token texts, 10 classes; "
+                "random-init weights, seed 42)",
+        "config": {
+            "workload": workload, "preset": None if custom else args.config, "model": spec.name,
+            "clients": K, "params": P, "local_steps": args.local_steps, "batch": rcfg.batch,
+            "defense": f"{defense}(f={f}, multi_k={multi_k})" if krum else defense, "attack": attack,
+            "attackers": f, "client_chunk": eng.trainer.chunks[0][1] - eng.trainer.chunks[0][0],
+            "parallelism": (f"clients sharded {K // world}/GPU x {world}; " + (
+                "one all-to-all (client rows -> coordinate ranges), per-GPU aggregation of its range, "
+                "all-gather of the aggregated vector" if sharded else "one all-gather of the client matrix")),
+            "exchange": eng.exchange,
+            "krum_distances": (None if not krum else "reference-exact (fp32 torch.norm accumulation, D bit-identical "
+                               "to krum.py:89-97)" if args.pairwise == "reference" else
+                               "centred Gram on MFMA + exact far-cluster refine"),
+            "training_phase": ("one captured HIP graph per round" if eng.use_graph else "eager launches") + (
+                ("; local updates = one flr_train_vit_bert call" if spec.family == "vit_bert" else
+                 "; local updates = one flr_train_clients_ex call") if eng.native else
+                "; local updates = the Python autograd composition of the kernels"),
+        },
+        "process_group": pg,
+        "full": args.full,
+    }
+    if not args.full:
+        # a plain run: the headline figure alone (everything below is --full)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        return
+
+    # ---- untimed diagnostics after the timed region (--full) ----
     eng.materialize()  # (FLR_DEFER_DEAD=2: the client matrix's dead-tap ranges, for the diagnostics below)
     reps = 5
-    sharded = eng.exchange == "alltoall"
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ev0.record()
     kw = {"publish": False} if hasattr(eng.defense, "publish") else {}
@@ -650,38 +742,7 @@ def main() -> None:
     global_sha256 = hashlib.sha256(eng.global_flat.detach().cpu().numpy().tobytes()).hexdigest()
     ref_sha = None if custom else REFERENCE_SHA.get((args.config, args.pairwise, args.warmup + args.steps))
 
-    out = {
-        "metric": METRIC,
-        "value": args.steps / elapsed,
-        "unit": "rounds/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "strong",
-        "vs_baseline": None,
-        "dtype": "f32 (bf16x6-split MFMA conv/GEMM = fp32 operands; Krum Gram bf16x4 hi/lo split, fp32 accumulate)",
-        "data": "synthetic (SURVEY §8d: N(0,1) 3x32x32 images, U{0..999} 16-token texts, 10 classes; "
-                "random-init weights, seed 42)",
-        "config": {
-            "workload": workload, "preset": None if custom else args.config, "model": spec.name,
-            "clients": K, "params": P, "local_steps": args.local_steps, "batch": rcfg.batch,
-            "defense": f"{defense}(f={f}, multi_k={multi_k})" if krum else defense, "attack": attack,
-            "attackers": f, "client_chunk": eng.trainer.chunks[0][1] - eng.trainer.chunks[0][0],
-            "parallelism": (f"clients sharded {K // world}/GPU x {world}; " + (
-                "one all-to-all (client rows -> coordinate ranges), per-GPU aggregation of its range, "
-                "all-gather of the aggregated vector" if sharded else "one all-gather of the client matrix")),
-            "exchange": eng.exchange,
-            "krum_distances": (None if not krum else "reference-exact (fp32 torch.norm accumulation, D bit-identical "
-                               "to krum.py:89-97)" if args.pairwise == "reference" else
-                               "centred Gram on MFMA + exact far-cluster refine"),
-            "training_phase": ("one captured HIP graph per round" if eng.use_graph else "eager launches") + (
-                ("; local updates = one flr_train_vit_bert call" if spec.family == "vit_bert" else
-                 "; local updates = one flr_train_clients_ex call") if eng.native else
-                "; local updates = the Python autograd composition of the kernels"),
-        },
-        "process_group": pg,
+    out.update({
         "global_sha256": global_sha256,
         "sha_matches_reference_run": None if ref_sha is None else global_sha256 == ref_sha,
         "aggregate_ms": aggregate_ms,
@@ -701,7 +762,7 @@ def main() -> None:
         "distance_phase": phase,
         "roofline": ref_roofline if ref_roofline is not None else gram_roofline,
         "roofline_gram": gram_roofline if ref_roofline is not None else None,
-    }
+    })
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(spec, P, K, defense, f, multi_k, args.local_steps, rcfg.batch,
                                            args.cpu_budget, dcfg.get("trim_ratio", 0.1))
