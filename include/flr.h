@@ -146,15 +146,11 @@ int flr_pairwise_l2_reference_tap(const float* X, int64_t K, int64_t P, int64_t 
  * (FLR_TC_DEFER_DEAD): its slab is read from gdead at the same training-order
  * offset, negated on rows k < nneg — the values flr_resnet_gru_fill_dead
  * writes, so D is bit-identical to the call on the filled X.  No dead column
- * may lie in the last P mod 8 (read from X): FLR_ERR_ARG.  after_rewrite
- * (a hipEvent_t, or NULL): recorded on the stream once the call has read
- * X for the last time (before the chain kernel of the last segment): the
- * dead slabs may be written from then on, beside the chains. */
+ * may lie in the last P mod 8 (read from X): FLR_ERR_ARG. */
 int flr_pairwise_l2_reference_tap_dead(const float* X, int64_t K, int64_t P, int64_t ldx,
                                        const int64_t* taps, int64_t ntaps, const uint64_t* dead,
                                        const float* gdead, int64_t nneg, double* D, void* ws,
-                                       size_t ws_bytes, int64_t part, int64_t nparts,
-                                       void* after_rewrite, void* stream);
+                                       size_t ws_bytes, int64_t part, int64_t nparts, void* stream);
 /* The same split over coordinate ranges held by different ranks (the
  * coordinate-sharded exchange): each range continues the chains where the
  * previous range left them.  _partial: `steps` chain steps of X (coordinates
@@ -801,9 +797,10 @@ int flr_train_clients(const flr_resnet_gru_spec* spec, const float* global, floa
  *   `global`, and only the aggregated P-vector is permuted back.
  * FLR_TC_DEFER_DEAD (with FLR_TC_TRAIN_ORDER) — the dead-tap ranges are left
  *   unwritten; the caller writes them with flr_resnet_gru_fill_dead before
- *   anything reads them (the round engine: on a side stream beside the Krum
- *   chains, whose tap rewrite reads those taps from `global` itself,
- *   flr_pairwise_l2_reference_tap_dead).
+ *   anything reads them from X (the round engine: only when something other
+ *   than its own Krum asks for the rows — the distances and the Multi-Krum
+ *   mean read those taps from `global` itself,
+ *   flr_pairwise_l2_reference_tap_dead / flr_rows_mean_dead).
  * Flag 0 is flr_train_clients. */
 #define FLR_TC_TRAIN_ORDER 1u
 #define FLR_TC_DEFER_DEAD 2u

@@ -9,13 +9,31 @@ client, as the reference does (krum.py:178-181).
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List
+from typing import Any, Dict, List, NamedTuple, Sequence, Tuple
 
 import torch
 
 from .. import ops
 from ..matrix import ClientMatrix
 from .base_defense import BaseDefense, Updates, as_matrix, source_device
+
+
+class DeadTaps(NamedTuple):
+    """A training-order client matrix whose dead-tap slabs are not written
+    (RoundEngine, FLR_DEFER_DEAD): every row's value there is g's, negated on
+    rows < nneg."""
+    masks: Sequence[int]               # per tap block the bitmask of its dead taps (the distances)
+    ranges: Sequence[Tuple[int, int]]  # the same slabs as (off, n) (the Multi-Krum mean, the selected row)
+    g: torch.Tensor                    # the training-order global vector the round trained from
+    nneg: int
+
+    @property
+    def taps(self):  # ops.pairwise_l2's dead=
+        return self.masks, self.g, self.nneg
+
+    @property
+    def rows(self):  # ops.rows_mean's dead=
+        return self.ranges, self.g, self.nneg
 
 
 class KrumDefense(BaseDefense):
@@ -33,14 +51,9 @@ class KrumDefense(BaseDefense):
         # reference mode over a training-order client matrix: its tap-major
         # convolution blocks [(off, Cout, Cin, KK), ...] (set by RoundEngine)
         self.tap_blocks = None
-        # ... and its dead-tap slabs not yet in X (masks per block, training-order
-        # global vector, negated rows; RoundEngine: FLR_TC_DEFER_DEAD), with the
-        # call that makes X whole before rows are read (the side-stream fill joined)
-        self.tap_dead = None
-        self.before_rows = None
-        # FLR_DEFER_DEAD=2: X's dead-tap ranges never written — (ranges, gtrain,
-        # nneg) for the Multi-Krum mean and the selected row
-        self.rows_dead = None
+        # ... whose dead-tap slabs are not written (DeadTaps; set and cleared by
+        # RoundEngine around its own call)
+        self.dead = None
         self.selected_clients: List[int] = []
         self.rejected_clients: List[int] = []
         self.client_scores: List[float] = []
@@ -58,10 +71,17 @@ class KrumDefense(BaseDefense):
         ref = self.pairwise_method == "reference"
         self.distances = ops.pairwise_l2(cm.X, self.pairwise_method, comm=self.comm,
                                          tap_blocks=self.tap_blocks if ref else None,
-                                         dead=self.tap_dead if ref and self.tap_blocks else None)
+                                         dead=self.dead and self.dead.taps if ref and self.tap_blocks else None)
         self._check_refine_capacity(n)
         self.scores_device, self.order_device = ops.krum_select(self.distances, f)
         return self.order_device
+
+    def _selected_row_filled(self, data: torch.Tensor, n: int) -> torch.Tensor:
+        """Single Krum's selected row data[i, :n], a copy with the unwritten
+        dead ranges filled in."""
+        i = int(self.order_device[0].item())
+        d = self.dead
+        return ops.fill_dead_ranges(data[i, :n].clone(), d.ranges, d.g, i < d.nneg)
 
     def _check_refine_capacity(self, K: int) -> None:
         """The Gram path's refine list holds 128 rows: every row at K <= 128.
@@ -80,15 +100,12 @@ class KrumDefense(BaseDefense):
         order = self.select(cm)
         if publish:
             self.publish()
-        if self.before_rows is not None:
-            self.before_rows()
         if self.multi_k == 1:
-            i = int(order[0].item())
-            if self.rows_dead is not None:
-                ranges, g, nneg = self.rows_dead
-                return ops.fill_dead_ranges(cm.data[i, : cm.P].clone(), ranges, g, i < nneg)
-            return cm.data[i, : cm.P]
-        return ops.rows_mean(cm.X, order[: min(self.multi_k, cm.K)], divisor=self.multi_k, dead=self.rows_dead)
+            if self.dead is not None:
+                return self._selected_row_filled(cm.data, cm.P)
+            return cm.data[int(order[0].item()), : cm.P]
+        return ops.rows_mean(cm.X, order[: min(self.multi_k, cm.K)], divisor=self.multi_k,
+                             dead=self.dead and self.dead.rows)
 
     # pairwise_method="reference" reproduces the reference's torch.norm
     # accumulation, which runs over the whole vector in parameters() order:
@@ -104,7 +121,7 @@ class KrumDefense(BaseDefense):
         return True
 
     # the round engine may leave X's dead-tap ranges unwritten (FLR_DEFER_DEAD):
-    # this defense reads them through tap_dead / rows_dead / before_rows
+    # this defense reads them through `dead`
     supports_dead_rows = True
 
     @property
@@ -116,6 +133,16 @@ class KrumDefense(BaseDefense):
         """Coordinate-sharded Krum (flr.shard): distances from the per-slice
         Gram sums of every GPU (bit-identical to the one-GPU D), scores and
         order replicated, then the Multi-Krum mean of this GPU's range."""
+        self._select_sharded(cs, publish, events)
+        if self.multi_k == 1:
+            if self.dead is not None:  # one GPU: the slice is the whole matrix
+                return self._selected_row_filled(cs.data, cs.n)
+            return cs.data[self.order_device[0].long(), : cs.n]
+        return ops.rows_mean(cs.X, self.order_device[: min(self.multi_k, cs.K)], divisor=self.multi_k,
+                             dead=self.dead and self.dead.rows)
+
+    def _select_sharded(self, cs, publish: bool, events=None) -> None:
+        """select() of a coordinate slice, then publish() if asked."""
         n, f = cs.K, self.num_malicious
         if n < 2 * f + 3:  # krum.py:153-157
             raise ValueError(
@@ -125,23 +152,13 @@ class KrumDefense(BaseDefense):
         self.scores_device, self.order_device = ops.krum_select(self.distances, f)
         if publish:
             self.publish()
-        if self.before_rows is not None:
-            self.before_rows()
-        if self.multi_k == 1:
-            if self.rows_dead is not None:  # one GPU: the slice is the whole matrix
-                i = int(self.order_device[0].item())
-                ranges, g, nneg = self.rows_dead
-                return ops.fill_dead_ranges(cs.data[i, : cs.n].clone(), ranges, g, i < nneg)
-            return cs.data[self.order_device[0].long(), : cs.n]
-        return ops.rows_mean(cs.X, self.order_device[: min(self.multi_k, n)], divisor=self.multi_k,
-                             dead=self.rows_dead)
 
     def _sharded_distances(self, cs, events=None):
         if self.pairwise_method == "reference":
             if cs.comm.world == 1:  # the one slice is the whole matrix
                 return ops.pairwise_l2(cs.X, "reference", tap_blocks=self.tap_blocks,
-                                       dead=self.tap_dead if self.tap_blocks else None)
-            if self.tap_dead is not None:
+                                       dead=self.dead and self.dead.taps if self.tap_blocks else None)
+            if self.dead is not None:
                 raise ValueError("deferred dead taps are a one-GPU mode")
             # training order: the rank boundaries are tap-block aligned (shard.aligned_bounds)
             return ops.pairwise_l2_reference_sharded(cs, self.tap_blocks)
@@ -231,15 +248,7 @@ class KrumTrimmedMeanDefense(KrumDefense):
         return self._combine(cm.X, order)
 
     def aggregate_sharded(self, cs, num_examples: List[int], publish: bool = True, events=None) -> torch.Tensor:
-        n, f = cs.K, self.num_malicious
-        if n < 2 * f + 3:  # krum.py:153-157
-            raise ValueError(
-                f"Krum requires n >= 2f + 3. Got n={n}, f={f}. Need at least {2 * f + 3} clients.")
-        self.distances = self._sharded_distances(cs, events)
-        self._check_refine_capacity(n)
-        self.scores_device, self.order_device = ops.krum_select(self.distances, f)
-        if publish:
-            self.publish()
+        self._select_sharded(cs, publish, events)
         return self._combine(cs.X, self.order_device)
 
     def aggregate(self, client_updates: Updates, num_examples: List[int]) -> List[torch.Tensor]:

@@ -52,13 +52,10 @@ def pairwise_l2(X: torch.Tensor, method: str = "gram", events=None, comm=None,
     comm: optional flr.shard.Comm for the reference mode: every rank holds the
     whole X, computes 1/world of the pair tiles and one all-reduce (sum, exact:
     one non-zero term per pair) of the 8·K² bytes of D gives every rank D.
-    dead: optional (masks, gdead, nneg[, mark]) with tap_blocks — X's dead-tap
-    slabs are not written yet (FLR_TC_DEFER_DEAD): bit t of masks[b] reads tap
-    t of block b from the training-order vector gdead, negated on rows < nneg
-    (flr_pairwise_l2_reference_tap_dead; the same D as on the filled X).
-    mark: an object with .event (a recorded-once torch.cuda.Event): recorded
-    on the stream once X has been read for the last time, then mark.recorded
-    = True (the round engine writes the slabs beside the chains from there)."""
+    dead: optional (masks, gdead, nneg) with tap_blocks — X's dead-tap slabs
+    are not written (FLR_TC_DEFER_DEAD): bit t of masks[b] reads tap t of
+    block b from the training-order vector gdead, negated on rows < nneg
+    (flr_pairwise_l2_reference_tap_dead; the same D as on the filled X)."""
     K, P, ldx = _check_matrix(X)
     D = torch.empty((K, K), dtype=torch.float64, device=X.device)
     if method == "reference":
@@ -76,17 +73,14 @@ def pairwise_l2(X: torch.Tensor, method: str = "gram", events=None, comm=None,
             _capi.call("flr_pairwise_l2_reference_tap", X.data_ptr(), K, P, ldx, ctypes.addressof(tarr),
                        len(taps) // 4, D.data_ptr(), wp, nbytes, part, nparts, _stream(X))
         else:
-            masks, gdead, nneg = dead[:3]
-            mark = dead[3] if len(dead) > 3 else None
+            masks, gdead, nneg = dead
             if len(masks) != len(taps) // 4 or gdead.device != X.device or gdead.dtype != torch.float32 \
                     or gdead.numel() < P:
                 raise ValueError("pairwise_l2(dead=): one mask per tap block and a float32 P-vector on X's device")
             marr = (ctypes.c_uint64 * max(1, len(masks)))(*[int(m) for m in masks])
             _capi.call("flr_pairwise_l2_reference_tap_dead", X.data_ptr(), K, P, ldx, ctypes.addressof(tarr),
                        len(taps) // 4, ctypes.addressof(marr), gdead.data_ptr(), int(nneg), D.data_ptr(), wp,
-                       nbytes, part, nparts, None if mark is None else mark.event.cuda_event, _stream(X))
-            if mark is not None:
-                mark.recorded = True
+                       nbytes, part, nparts, _stream(X))
         if nparts > 1:
             comm.all_reduce_sum(D)
         return D

@@ -31,6 +31,7 @@ from . import dist as fdist
 from . import ops
 from .attacks import Backdoor, poison_batches_
 from .defenses import get_defense
+from .defenses.krum import DeadTaps
 from .matrix import ClientMatrix
 from .shard import PW_SLICES, Comm, CoordExchange, aligned_bounds
 from .models.multimodal import ModelSpec, model_class, param_layout
@@ -65,28 +66,13 @@ def initial_global(spec: ModelSpec, seed: int, device) -> torch.Tensor:
     return torch.cat([p.detach().reshape(-1) for p in m.parameters()]).to(device)
 
 
-class _DeadFill:
-    """The deferred dead-tap fill of a round (RoundEngine, FLR_DEFER_DEAD):
-    side stream, the distances' 'X read for the last time' mark, the fill's
-    done event, per-block dead-tap masks; state 0 idle, 1 due this round."""
-
-    class _Mark:
-        def __init__(self, device):
-            self.event = torch.cuda.Event()
-            self.event.record(torch.cuda.current_stream(device))  # created now: a handle to pass down
-            self.recorded = False
-
-    def __init__(self, device, masks):
-        self.side = torch.cuda.Stream(device)
-        self.mark = _DeadFill._Mark(device)
-        self.done = torch.cuda.Event()
-        self.masks = masks
-        self.state = 0
-
-
 class RoundEngine:
     def __init__(self, spec: ModelSpec, rcfg: RoundConfig, tcfg: TrainConfig = TrainConfig(), device="cuda",
                  rank: int = 0, world: int = 1):
+        defer = os.environ.get("FLR_DEFER_DEAD", "2")
+        if defer == "1":  # loud: an old A/B script must not report numbers for another mode
+            raise ValueError("FLR_DEFER_DEAD=1 (the dead-tap fill on a side stream beside the Krum chains) was "
+                             "removed: measured slower in every variant (profiles/r6_dead/); use 0, or 2 (the default)")
         self.spec, self.rcfg, self.tcfg = spec, rcfg, tcfg
         self.device = torch.device(device)
         self.rank, self.world = rank, world
@@ -117,9 +103,8 @@ class RoundEngine:
         if mode == "alltoall" and not self.defense.supports_sharded:
             raise ValueError(f"{self.defense!r} needs whole client rows: use exchange='allgather'")
         self.exchange = mode
-        self.full = None
         self.xchg = None
-        self.slice = None
+        self._full = self._slice = None  # outside readers: the full / slice properties (they make X whole first)
         self.global_flat = initial_global(spec, rcfg.seed, self.device)
         steps = tcfg.local_steps
         self.batches = synthetic_batches(spec, steps, range(self.lo, self.hi), rcfg.batch, self.device)
@@ -155,38 +140,31 @@ class RoundEngine:
         if mode == "alltoall":
             self.xchg = CoordExchange(K, self.hi - self.lo, self.trainer.P, self.device, Comm(), bounds=bounds)
         else:
-            self.full = self.trainer.X if world == 1 else ClientMatrix.empty(K, shapes, self.device)
+            self._full = self.trainer.X if world == 1 else ClientMatrix.empty(K, shapes, self.device)
             if world > 1 and hasattr(self.defense, "comm"):
                 # whole rows on every rank: the reference-exact Krum distances
                 # split their pair tiles over the ranks (one 8·K² all-reduce)
                 self.defense.comm = Comm()
         self.gtrain = self.trainer.to_train_order(self.global_flat) if self.train_order else None
-        # FLR_DEFER_DEAD=1 (opt-in): the dead-tap slabs (copies of the global
-        # model, 58 % of P at C3) written by a side stream under the Krum chains
-        # instead of last in the training phase, the tap rewrite reading them from
-        # gtrain meanwhile.  Bit-identical, but the chains slow by more than the
-        # fill saves (profiles/r6_dead/): off by default
-        # FLR_DEFER_DEAD=2 (default): never written at all — the distances read
-        # them from the round's global vector, the Multi-Krum mean too
-        # (flr_rows_mean_dead): C3 15.65-15.73 -> 15.94-15.99 rounds/s, the
-        # same bits (profiles/r6_dead/); materialize() writes them for any other
-        # reader of X; =0: written last in the training phase
-        self._fill = None
-        self._lazy = None
-        self._x_stale = False
-        defer = os.environ.get("FLR_DEFER_DEAD", "2")
+        # FLR_DEFER_DEAD=2 (default): the dead-tap slabs (copies of the global
+        # model, 58 % of P at C3) are not written by the round at all — the
+        # distances read them from the round's global vector, the Multi-Krum
+        # mean too (flr_rows_mean_dead): C3 15.65-15.73 -> 15.94-15.99 rounds/s,
+        # the same bits (profiles/r6_dead/); materialize() writes them for any
+        # other reader of X (the full / slice / client_matrix properties call
+        # it); =0: written last in the training phase
+        self._dead: Optional[DeadTaps] = None
+        self._x_stale = False  # set where run_round arms the deferral, cleared by materialize() alone
         if (self.train_order and world == 1 and self.defense.__dict__.get("tap_blocks")
                 and getattr(self.defense, "supports_dead_rows", False)
-                and hasattr(self.trainer, "fill_dead") and defer in ("1", "2")):
+                and hasattr(self.trainer, "fill_dead") and defer == "2"):
             masks = self._dead_masks(self.defense.tap_blocks)
             if masks is not None and any(masks):
                 self.trainer.defer_dead = True
-                if defer == "1":
-                    self._fill = _DeadFill(self.device, masks)
-                else:
-                    # the global vector the round trained from (gtrain is overwritten by the publish)
-                    self._lazy = (masks, self.trainer.dead_ranges(),
-                                  torch.empty(self.trainer.P, dtype=torch.float32, device=self.device))
+                # g: the global vector the round trained from (gtrain is overwritten by the publish)
+                self._dead = DeadTaps(masks, self.trainer.dead_ranges(),
+                                      torch.empty(self.trainer.P, dtype=torch.float32, device=self.device),
+                                      self._num_flipped())
 
         self.round_index = 0
         self.fell_back = False
@@ -244,31 +222,37 @@ class RoundEngine:
         return masks
 
     def materialize(self) -> None:
-        """X's dead-tap ranges written (FLR_DEFER_DEAD=2 leaves them out): call
-        before reading the client matrix outside the round's own Krum."""
-        if self._lazy is not None and self._x_stale:
-            self.trainer.fill_dead(self._lazy[2], self._num_flipped())
+        """X's dead-tap ranges written (FLR_DEFER_DEAD=2 leaves them out), from
+        the global vector the last round trained from.  Idempotent; the
+        full / slice / client_matrix properties call it."""
+        if self._x_stale:
+            self.trainer.fill_dead(self._dead.g, self._dead.nneg)
             self._x_stale = False
 
-    def _join_fill(self) -> None:
-        """X whole on the current stream: this round's dead-tap fill launched
-        if it is not yet (on the side stream, after the distances' last read
-        of X when they marked it, else after everything so far) and waited for.
-        Idempotent; a no-op without a pending fill."""
-        f = self._fill
-        if f is None or f.state == 0:
-            return
-        main = torch.cuda.current_stream(self.device)
-        if f.state == 1:
-            if f.mark.recorded:
-                f.side.wait_event(f.mark.event)
-            else:
-                f.side.wait_stream(main)
-            with torch.cuda.stream(f.side):
-                self.trainer.fill_dead(self.gtrain, self._num_flipped())
-                f.done.record(f.side)
-        main.wait_event(f.done)
-        f.state = 0
+    @property
+    def dead_deferred(self) -> bool:
+        """The rounds leave X's dead-tap ranges unwritten (FLR_DEFER_DEAD=2)."""
+        return self._dead is not None
+
+    @property
+    def client_matrix(self) -> ClientMatrix:
+        """This rank's rows of the client matrix, whole: the supported way to
+        read them (eng.trainer.X is the trainer's raw buffer, whose dead-tap
+        ranges a round may have left unwritten)."""
+        self.materialize()
+        return self.trainer.X
+
+    @property
+    def full(self) -> Optional[ClientMatrix]:
+        """The all-gather exchange's K×P matrix of the last round, whole."""
+        self.materialize()
+        return self._full
+
+    @property
+    def slice(self):
+        """The all-to-all exchange's coordinate slice of the last round, whole."""
+        self.materialize()
+        return self._slice
 
     def _num_flipped(self) -> int:
         """Local rows of sign-flip attackers (clients 0..f-1): they submit
@@ -323,52 +307,38 @@ class RoundEngine:
             self.losses = self._graph_losses
         else:
             self.losses = self._train_phase()
-        if self._fill is not None:
-            # the dead-tap slabs are written by the side stream under the Krum
-            # chains (launched by _join_fill before the rows are read); until
-            # then the distances read those taps from gtrain (ops.pairwise_l2 dead=)
-            f = self._fill
-            f.state, f.mark.recorded = 1, False
-            self.defense.tap_dead = (f.masks, self.gtrain, self._num_flipped(), f.mark)
-            self.defense.before_rows = self._join_fill
-        if self._lazy is not None:
-            masks, ranges, gprev = self._lazy
-            _capi.call("flr_copy_rows", self.gtrain.data_ptr(), self.trainer.P, self.trainer.P, gprev.data_ptr(),
-                       self.trainer.P, 1, torch.cuda.current_stream(self.device).cuda_stream)
-            nneg = self._num_flipped()
-            self._x_stale = True
-            self.defense.tap_dead = (masks, gprev, nneg)
-            self.defense.rows_dead = (ranges, gprev, nneg)
+        if self._dead is None:
+            return self._aggregate_phase()
+        # the training phase left X's dead-tap slabs out: the defense reads them
+        # from this round's global vector, every other reader after materialize()
+        _capi.call("flr_copy_rows", self.gtrain.data_ptr(), self.trainer.P, self.trainer.P, self._dead.g.data_ptr(),
+                   self.trainer.P, 1, torch.cuda.current_stream(self.device).cuda_stream)
+        self._x_stale = True
+        self.defense.dead = self._dead
         try:
             return self._aggregate_phase()
         finally:
-            self._join_fill()  # X is whole for every later reader
-            if self._fill is not None:
-                self.defense.tap_dead = self.defense.before_rows = None
-            if self._lazy is not None:
-                self.defense.tap_dead = self.defense.rows_dead = None
+            self.defense.dead = None
 
     def _aggregate_phase(self) -> torch.Tensor:
         kw = {"publish": False} if hasattr(self.defense, "publish") else {}
         self.fell_back = False
         self.fallback_error = None
         if self.exchange == "alltoall":
-            self.slice = self.xchg.exchange(self.trainer.X.data)
+            cs = self._slice = self.xchg.exchange(self.trainer.X.data)
             try:
-                part = self.defense.aggregate_sharded(self.slice, self.num_examples, **kw)
+                part = self.defense.aggregate_sharded(cs, self.num_examples, **kw)
             except Exception as e:  # noqa: BLE001 - the reference catches any exception
-                part = self._fallback(e, self.slice.X)
-            self._join_fill()  # gtrain is overwritten next: the fill has read it
-            self.slice.gather_vector(part, self.gtrain if self.train_order else self.global_flat)
+                part = self._fallback(e, cs.X)
+            cs.gather_vector(part, self.gtrain if self.train_order else self.global_flat)
             return self._publish()
-        fdist.allgather_rows(self.trainer.X.data, self.full.data)
+        fdist.allgather_rows(self.trainer.X.data, self._full.data)
         if self._wants_global:  # FLTrust: the server update starts from this round's global model
             kw["global_flat"] = self.global_flat.clone()  # global_flat is overwritten below
         try:
-            agg = self.defense.aggregate_flat(self.full, self.num_examples, **kw)
+            agg = self.defense.aggregate_flat(self._full, self.num_examples, **kw)
         except Exception as e:  # noqa: BLE001
-            agg = self._fallback(e, self.full.X)
-        self._join_fill()
+            agg = self._fallback(e, self._full.X)
         return self._publish(agg)
 
     def _fallback(self, err: Exception, X: torch.Tensor) -> torch.Tensor:
@@ -377,16 +347,14 @@ class RoundEngine:
         The reference catches every Exception; RoundConfig.fallback_device_errors
         = False keeps device / library failures (kernel launch, workspace, HIP or
         RCCL errors, out of memory) loud instead."""
-        from ._capi import FlrError
-        self._join_fill()
-        self.materialize()
-        device_error = isinstance(err, (FlrError, torch.cuda.OutOfMemoryError))
+        device_error = isinstance(err, (_capi.FlrError, torch.cuda.OutOfMemoryError))
         if not self.rcfg.fallback_fedavg or (device_error and (not self.rcfg.fallback_device_errors
                                                                or self.world > 1)):
-            raise err
+            raise err  # decided before anything is launched: the defense's own error propagates
         logging.getLogger(__name__).error("Defense aggregation failed: %s, falling back to FedAvg", err)
         self.fell_back = True
         self.fallback_error = type(err).__name__
+        self.materialize()  # FedAvg reads whole rows
         return ops.fedavg(X, self.num_examples)
 
     # ---- checkpoint / resume (run_experiments.py:268-279) ----------------------

@@ -132,10 +132,9 @@ def test_c3_trained_round_krum_indices_vs_reference_norms(cuda):
     glob = eng.global_flat.clone().cpu()
     new = eng.run_round().clone().cpu()
     eng.defense.publish()
-    eng.materialize()  # the client matrix whole (the dead-tap ranges, FLR_DEFER_DEAD)
-    torch.cuda.synchronize()
     P = eng.trainer.P
-    X = eng.trainer.X.data[:, :P]
+    X = eng.client_matrix.data[:, :P]  # whole (the dead-tap ranges, FLR_DEFER_DEAD)
+    torch.cuda.synchronize()
     D_gpu = eng.defense.distances.double()
     D64 = fp64_distances(X, P)
     t0 = time.perf_counter()
@@ -257,8 +256,7 @@ def _tail_param_report(eng, spec, new, rows, glob, name="fc2.bias"):
 def _sample_rows(eng, clients, idx: torch.Tensor) -> torch.Tensor:
     """[len(clients), len(idx)] host copy of the client rows' torch-order
     coordinates idx (one row converted at a time)."""
-    eng.materialize()
-    X = eng.trainer.X.data[:, : eng.trainer.P]
+    X = eng.client_matrix.data[:, : eng.trainer.P]
     di = idx.to(X.device)
     out = []
     for k in clients:
@@ -271,14 +269,14 @@ def _check_clients(eng, spec, glob, clients, batches_dev, masks_dev, negate=(), 
     """Sampled clients' rows vs the oracle loop: whole vector at 1e-5 and the
     per-tensor update report (tests/parity.py); returns the reports."""
     reps = {}
-    eng.materialize()
+    X = eng.client_matrix.data
     for k in clients:
         j = k - eng.lo
         cb = [(im[j].cpu(), tk[j].cpu(), lb[j].cpu()) for im, tk, lb in batches_dev]
         cm = None if masks_dev is None else [m[j].cpu() for m in masks_dev]
         upd, ref_loss = otrain.local_update(model_class(spec), spec, glob, cb, masks=cm)
         ref = torch.cat([u.reshape(-1) for u in upd])
-        row = eng.trainer.X.data[j, : eng.trainer.P]
+        row = X[j, : eng.trainer.P]
         row = eng.trainer.to_torch_order(row) if eng.train_order else row
         reps[f"client{k}"] = delta_report(-row if k in negate else row, ref, glob, param_layout(spec))
         if losses:

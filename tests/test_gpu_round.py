@@ -187,18 +187,16 @@ def test_native_trainer_round_equals_python_trainer(cuda, monkeypatch, order):
     assert torch.equal(ga, gb)
 
 
-@pytest.mark.parametrize("defer,multi_k", [("1", 4), ("1", 1), ("2", 4), ("2", 1)])
+@pytest.mark.parametrize("defer,multi_k", [("2", 4), ("2", 1)])
 def test_deferred_dead_taps_bit_identical(cuda, monkeypatch, defer, multi_k):
-    """FLR_DEFER_DEAD=1 (opt-in): the training phase leaves X's dead-tap slabs
-    to a side-stream fill beside the reference-exact Krum distances, which
-    read those taps from the global vector meanwhile; =2: never written — the
-    distances and the Multi-Krum mean (flr_rows_mean_dead; the selected row
-    itself at multi_k = 1) read them from the round's global vector, and
-    materialize() writes them for other readers.  Against the slabs written
-    last in the training phase (FLR_DEFER_DEAD=0): the same distance matrix,
-    selection, client matrix and global model bit for bit, over 2 rounds of
-    HIP-graph replay with sign-flip attackers, on the full ResNet-18 + GRU
-    model (dead taps in layers 3-4)."""
+    """FLR_DEFER_DEAD=2: the training phase never writes X's dead-tap slabs —
+    the reference-exact Krum distances and the Multi-Krum mean
+    (flr_rows_mean_dead; the selected row itself at multi_k = 1) read them
+    from the round's global vector, and reading eng.client_matrix writes them
+    for other readers.  Against the slabs written last in the training phase
+    (FLR_DEFER_DEAD=0): the same distance matrix, selection, client matrix and
+    global model bit for bit, over 2 rounds of HIP-graph replay with sign-flip
+    attackers, on the full ResNet-18 + GRU model (dead taps in layers 3-4)."""
     from flr.models.multimodal import ModelSpec
     spec = ModelSpec()
     rc = RoundConfig(num_clients=8, batch=4, defense="krum", attack="sign_flip", num_attackers=1,
@@ -207,13 +205,12 @@ def test_deferred_dead_taps_bit_identical(cuda, monkeypatch, defer, multi_k):
     for d in ("0", defer):
         monkeypatch.setenv("FLR_DEFER_DEAD", d)
         eng = RoundEngine(spec, rc, TrainConfig(local_steps=2), cuda)
-        assert eng.train_order and (eng._fill is not None) == (d == "1") and (eng._lazy is not None) == (d == "2")
+        assert eng.train_order and eng.dead_deferred == (d == "2")
         for _ in range(2):
             eng.run_round()
         eng.defense.publish()
-        eng.materialize()
         res.append((eng.global_flat.clone().cpu(), eng.defense.distances.clone().cpu(),
-                    list(eng.defense.selected_clients), eng.trainer.X.X.clone().cpu()))
+                    list(eng.defense.selected_clients), eng.client_matrix.X.clone().cpu()))
     (ga, da, sa, xa), (gb, db, sb, xb) = res
     assert torch.isfinite(ga).all() and torch.isfinite(da).all()
     assert torch.equal(da, db) and sa == sb
@@ -233,7 +230,7 @@ def test_dead_deferral_only_where_the_defense_reads_it(cuda, monkeypatch):
     kw = dict(num_clients=8, batch=4, attack="sign_flip", num_attackers=1)
     eng = RoundEngine(spec, RoundConfig(defense="krum", defense_cfg={"multi_k": 4}, **kw),
                       TrainConfig(local_steps=1), cuda)
-    assert eng._lazy is not None and eng.trainer.defer_dead
+    assert eng.dead_deferred
     outs = []
     for d in (None, "0"):
         if d is not None:
@@ -241,6 +238,77 @@ def test_dead_deferral_only_where_the_defense_reads_it(cuda, monkeypatch):
         eng = RoundEngine(spec, RoundConfig(defense="krum_trimmed_mean", defense_cfg={"multi_k": 6,
                                                                                        "trim_ratio": 0.2}, **kw),
                           TrainConfig(local_steps=1), cuda)
-        assert eng.train_order and eng._lazy is None and eng._fill is None and not eng.trainer.defer_dead
+        assert eng.train_order and not eng.dead_deferred
         outs.append(eng.run_round().clone().cpu())
     assert torch.isfinite(outs[0]).all() and torch.equal(outs[0], outs[1])
+
+
+def _dead_tap_spec():
+    """The smallest model here whose rounds defer dead taps: 64-wide stages are
+    tap-major, and layers 3-4 (2x2 and 1x1 maps) have dead taps — 53,248 of
+    321,258 coordinates in 4 ranges."""
+    from flr.models.multimodal import ModelSpec
+    return ModelSpec(widths=(64, 64, 64, 64), blocks=(1, 1, 1, 1), vocab=50, embed=8, hidden=16, fusion=16,
+                     dropout=0.0)
+
+
+def _krum_engine(cuda, monkeypatch, defer, **rc):
+    monkeypatch.setenv("FLR_DEFER_DEAD", defer)
+    kw = dict(num_clients=8, batch=4, defense="krum", attack="sign_flip", num_attackers=1,
+              defense_cfg={"pairwise_method": "reference", "multi_k": 4})
+    kw.update(rc)
+    eng = RoundEngine(_dead_tap_spec(), RoundConfig(**kw), TrainConfig(local_steps=2), cuda)
+    assert eng.train_order and eng.dead_deferred == (defer == "2")
+    return eng
+
+
+@pytest.mark.parametrize("exchange", ["alltoall", "allgather"])
+def test_outside_reads_of_the_client_matrix_are_whole(cuda, monkeypatch, exchange):
+    """With the dead-tap deferral (FLR_DEFER_DEAD=2) no reader has to remember
+    a fill: eng.client_matrix and the exchange's own view (eng.slice /
+    eng.full), read after each of 2 rounds with no materialize() call, equal
+    the same reads on an engine that writes the slabs in the training phase
+    (FLR_DEFER_DEAD=0) bit for bit — whichever of the two is read first — and
+    the fill between the rounds does not disturb the replayed graph: the same
+    global model after round 2."""
+    res = []
+    for d in ("0", "2"):
+        eng = _krum_engine(cuda, monkeypatch, d, exchange=exchange)
+        assert eng.exchange == exchange
+        reads = []
+        for view_first in (True, False):
+            eng.run_round()
+            for view in (view_first, not view_first):
+                m = (eng.slice if exchange == "alltoall" else eng.full) if view else eng.client_matrix
+                reads.append(m.X.clone().cpu())
+        res.append((reads, eng.global_flat.clone().cpu()))
+    (ra, ga), (rb, gb) = res
+    assert torch.isfinite(ga).all() and all(torch.isfinite(x).all() for x in ra)
+    assert len(ra) == len(rb) == 4
+    for a, b in zip(ra, rb):
+        assert torch.equal(a, b)
+    assert torch.equal(ga, gb)
+
+
+def test_defense_error_propagates_with_nothing_launched_before(cuda, monkeypatch):
+    """n = 8 < 2f + 3 = 9: Krum raises before any distance kernel
+    (krum.py:153-157).  Without fallback_fedavg run_round raises that
+    ValueError itself, and the client matrix read afterwards is whole (equal
+    to the FLR_DEFER_DEAD=0 engine's); with it the round is ops.fedavg of the
+    whole matrix."""
+    from flr import ops
+    want = "Krum requires n >= 2f + 3. Got n=8, f=3. Need at least 9 clients."
+    X = []
+    for d in ("0", "2"):
+        eng = _krum_engine(cuda, monkeypatch, d, num_attackers=3)
+        with pytest.raises(ValueError) as ei:
+            eng.run_round()
+        assert type(ei.value) is ValueError and str(ei.value) == want
+        assert not eng.fell_back and eng.defense.dead is None
+        X.append(eng.client_matrix.data.clone()[:, : eng.trainer.P])  # the rows' own leading dimension
+    assert torch.isfinite(X[0]).all() and torch.equal(X[0], X[1])
+    eng = _krum_engine(cuda, monkeypatch, "2", num_attackers=3, fallback_fedavg=True)
+    got = eng.run_round().clone()
+    assert eng.fell_back and eng.fallback_error == "ValueError"
+    assert torch.equal(got, eng.trainer.to_torch_order(ops.fedavg(X[0], eng.num_examples)))
+    assert torch.equal(eng.client_matrix.X, X[0])

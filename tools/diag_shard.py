@@ -36,7 +36,7 @@ def worker(rank, world, port, graph, q):
         torch.cuda.synchronize()
         eng.defense.publish()
         D = eng.defense.distances
-        out.append((g0.cpu().numpy(), eng.trainer.X.X.cpu().numpy(), list(eng.defense.selected_clients),
+        out.append((g0.cpu().numpy(), eng.client_matrix.X.cpu().numpy(), list(eng.defense.selected_clients),
                     g.cpu().numpy().copy(), None if D is None else D.cpu().numpy()))
     q.put((rank, out))
     if world > 1:

@@ -25,12 +25,12 @@ def main():
                       TrainConfig(local_steps=5), dev)
     g = eng.run_round()
     torch.cuda.synchronize()
-    print("c3", "X", sha(eng.trainer.X.data), "global", sha(g), flush=True)
+    print("c3", "X", sha(eng.client_matrix.data), "global", sha(g), flush=True)
     eng = RoundEngine(VIT_BERT, RoundConfig(num_clients=2, batch=8, num_attackers=0, attack="none", defense="fedavg"),
                       TrainConfig(local_steps=1), dev)
     g = eng.run_round()
     torch.cuda.synchronize()
-    print("c4", "X", sha(eng.trainer.X.data), "global", sha(g), flush=True)
+    print("c4", "X", sha(eng.client_matrix.data), "global", sha(g), flush=True)
 
 
 if __name__ == "__main__":
