@@ -251,6 +251,40 @@ int flr_trimmed_mean_rows(const float* X, int64_t K, int64_t P, int64_t ldx, con
 int flr_median_lower_rows(const float* X, int64_t K, int64_t P, int64_t ldx, const int32_t* rows, int64_t m,
                           float* out, void* stream);
 
+/* ---- Bulyan (El Mhamdi, Guerraoui, Rouault, ICML 2018) ------------------
+ * Stage 2, the median-window mean over the m rows rows[0..m) of X (rows NULL:
+ * rows 0..m-1; m = K is the whole matrix), m <= 128.  Per coordinate: sort
+ * ascending into s[0..m), med = s[(m-1)/2] (the lower median); take the beta
+ * ranks with the smallest fp32 |s[r] - med|, equal distances to the smaller
+ * value — a window [lo, lo+beta) around the median rank; sum it in rank order
+ * (sequential fp32 adds from 0.f, no FMA) and divide once by beta.  beta = m is
+ * the mean of all rows in rank order, beta = 1 the lower median.  NaNs sort
+ * last; the result is NaN when the column holds more than m - beta of them or
+ * the median rank is one.  Columns holding +-inf: unspecified, read in bounds.
+ * FLR_ERR_ARG: null X / out, m < 1, m > K, beta < 1, beta > m, ldx < P;
+ * FLR_ERR_UNSUPPORTED: m > 128.  rows as flr_rows_mean (clamped on the device). */
+int flr_median_window_mean_rows(const float* X, int64_t K, int64_t P, int64_t ldx, const int32_t* rows,
+                                int64_t m, int64_t beta, float* out, void* stream);
+
+/* Stage 1, the iterated Krum selection on the fp64 distance matrix D (device,
+ * K×K row-major), all on the device, no host synchronisation.  alive = every
+ * client; theta times, with n_r clients alive: m_r = min(n_r - 1, max(1, n_r -
+ * f - 2)); an alive client's score is the numpy pairwise sum of ranks 1..m_r of
+ * its sorted distances to the alive clients (Krum's rule on the sub-matrix);
+ * the smallest score is picked (exact ties: the lowest client index; NaN scores
+ * last) and leaves the alive set.
+ * scores: device fp64 [K], the first iteration's scores (flr_krum_select's, bit
+ * for bit, where that call is defined).  picked: device int32 [K], the theta
+ * picks in pick order, then the unpicked clients in ascending index.  Every
+ * slot of both is written on every call.
+ * FLR_ERR_ARG: null pointer, K < 1, f < 0, theta outside [1, K];
+ * FLR_ERR_UNSUPPORTED: K > 1024; FLR_ERR_WORKSPACE: workspace null or smaller
+ * than flr_krum_select_iter_workspace(K) (0 for K <= 0).  Bulyan's n >= 4f + 3
+ * is the caller's rule. */
+size_t flr_krum_select_iter_workspace(int64_t K);
+int flr_krum_select_iter(const double* D, int64_t K, int64_t f, int64_t theta, double* scores,
+                         int32_t* picked, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- a6 + a7: fused gradient clip + SGD-momentum step -----------------
  * Replaces, for every client row at once, clip_grad_norm_(params, max_norm)
  * + torch.optim.SGD(lr, momentum, weight_decay).step()

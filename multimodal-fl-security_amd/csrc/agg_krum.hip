@@ -99,6 +99,111 @@ __global__ __launch_bounds__(1024) void order_kernel(const double* __restrict__ 
   }
 }
 
+// ---- Bulyan's first stage: Krum re-run on the shrinking set ---------------------
+// theta + 1 stream-ordered launches of one kernel, no host round trip.  Launch
+// `it` first closes iteration it - 1: every workgroup rebuilds the alive set
+// (every client not in picked[0, it - 1), written by earlier launches) and
+// takes the argmin of that iteration's scores over it itself (K values: cheaper
+// than a launch of its own), workgroup 0 records the pick.  It then scores its
+// own client for iteration `it` against the clients still alive, as
+// score_kernel does on the whole row: the dead columns are loaded as the NaN
+// padding, which sorts after every value, and ranks 1..m of the sorted row
+// hold alive entries only (m <= n_r - 1).  The scores are double-buffered by
+// iteration parity: a workgroup writes iteration it's while others still read
+// iteration it - 1's.  Launch theta only closes the last iteration and lists
+// the unpicked clients in ascending index.
+constexpr int ITER_THREADS = 256;
+
+// (sa, ia) is picked before (sb, ib): the smaller score, an exact tie to the
+// lower index, NaN last; index -1 is no candidate
+__device__ __forceinline__ bool picks_before(double sa, int ia, double sb, int ib) {
+  if (ia < 0) return false;
+  if (ib < 0) return true;
+  return np_after(sb, sa) || (np_equal(sa, sb) && ia < ib);
+}
+
+__global__ __launch_bounds__(ITER_THREADS) void iter_kernel(const double* __restrict__ D, int K, int f, int it,
+                                                            int theta, double* __restrict__ sc,
+                                                            double* __restrict__ scores,
+                                                            int32_t* __restrict__ picked) {
+  __shared__ double s[MAXK];
+  __shared__ unsigned char alive[MAXK];
+  __shared__ double rs[ITER_THREADS];
+  __shared__ int ri[ITER_THREADS];
+  const int tid = threadIdx.x;
+  for (int j = tid; j < K; j += ITER_THREADS) alive[j] = 1;
+  __syncthreads();
+  for (int j = tid; j < it - 1; j += ITER_THREADS) alive[min(max(picked[j], 0), K - 1)] = 0;
+  __syncthreads();
+  if (it > 0) {
+    const double* prev = sc + (size_t)((it - 1) & 1) * K;
+    double bs = 0.0;
+    int bi = -1;
+    for (int j = tid; j < K; j += ITER_THREADS) {  // ascending j: a tie keeps the lower index
+      if (!alive[j]) continue;
+      const double sj = prev[j];
+      if (picks_before(sj, j, bs, bi)) {
+        bs = sj;
+        bi = j;
+      }
+    }
+    rs[tid] = bs;
+    ri[tid] = bi;
+    __syncthreads();
+    for (int w = ITER_THREADS / 2; w > 0; w >>= 1) {
+      if (tid < w && picks_before(rs[tid + w], ri[tid + w], rs[tid], ri[tid])) {
+        rs[tid] = rs[tid + w];
+        ri[tid] = ri[tid + w];
+      }
+      __syncthreads();
+    }
+    const int pick = min(max(ri[0], 0), K - 1);  // an alive client always exists (it - 1 < theta <= K)
+    if (tid == 0) {
+      alive[pick] = 0;
+      if (blockIdx.x == 0) picked[it - 1] = pick;
+    }
+    __syncthreads();
+  }
+  if (it >= theta) {  // the closing launch: the unpicked clients, ascending
+    if (blockIdx.x == 0 && tid == 0) {
+      int n = theta;
+      for (int j = 0; j < K; ++j)
+        if (alive[j] && n < K) picked[n++] = j;
+    }
+    return;
+  }
+  const int i = blockIdx.x;
+  if (!alive[i]) return;
+  const int nr = K - it;
+  const int m = min(nr - 1, max(1, nr - f - 2));
+  int np2 = 1;
+  while (np2 < K) np2 <<= 1;
+  for (int j = tid; j < np2; j += ITER_THREADS)
+    s[j] = (j < K && alive[j]) ? D[(int64_t)i * K + j] : __builtin_nan("");
+  __syncthreads();
+  for (int k = 2; k <= np2; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int idx = tid; idx < np2; idx += ITER_THREADS) {
+        const int ixj = idx ^ j;
+        if (ixj > idx) {
+          const double a = s[idx], b = s[ixj];
+          const bool up = (idx & k) == 0;
+          if ((up && np_after(a, b)) || (!up && np_after(b, a))) {
+            s[idx] = b;
+            s[ixj] = a;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (tid == 0) {
+    const double v = 0.0 + np_pairwise_sum<4>(s + 1, m);
+    sc[(size_t)(it & 1) * K + i] = v;
+    if (it == 0) scores[i] = v;
+  }
+}
+
 }  // namespace krum
 }  // namespace flr
 
@@ -116,4 +221,25 @@ extern "C" int flr_krum_select(const double* D, int64_t K, int64_t f, double* sc
   if (rc != FLR_OK) return rc;
   hipLaunchKernelGGL(krum::order_kernel, dim3(1), dim3(1024), 0, st, scores, (int)K, order);
   return launch_status("krum order_kernel");
+}
+
+extern "C" size_t flr_krum_select_iter_workspace(int64_t K) {
+  return K > 0 ? (size_t)K * 2 * sizeof(double) : 0;  // the scores of two successive iterations
+}
+
+extern "C" int flr_krum_select_iter(const double* D, int64_t K, int64_t f, int64_t theta, double* scores,
+                                    int32_t* picked, void* workspace, size_t workspace_bytes, void* stream) {
+  if (K < 1 || f < 0 || theta < 1 || theta > K || !D || !scores || !picked) return FLR_ERR_ARG;
+  if (K > krum::MAXK) return FLR_ERR_UNSUPPORTED;
+  if (!workspace || workspace_bytes < flr_krum_select_iter_workspace(K)) return FLR_ERR_WORKSPACE;
+  hipStream_t st = as_stream(stream);
+  double* sc = static_cast<double*>(workspace);
+  for (int it = 0; it <= (int)theta; ++it) {
+    const int grid = it < (int)theta ? (int)K : 1;
+    hipLaunchKernelGGL(krum::iter_kernel, dim3(grid), dim3(krum::ITER_THREADS), 0, st, D, (int)K, (int)f, it,
+                       (int)theta, sc, scores, picked);
+    const int rc = launch_status("krum iter_kernel");
+    if (rc != FLR_OK) return rc;
+  }
+  return FLR_OK;
 }

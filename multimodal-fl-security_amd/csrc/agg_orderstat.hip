@@ -146,6 +146,128 @@ __global__ __launch_bounds__(THREADS, 3) void orderstat_kernel(const float* __re
   }
 }
 
+// ---- Bulyan's second stage: the mean of the beta values closest to the median ----
+// (El Mhamdi, Guerraoui, Rouault, ICML 2018.)  Over the sorted column s[0, m),
+// med = s[(m-1)/2], the beta ranks with the smallest fp32 |s[r] - med| (ties to
+// the smaller value) are a window [lo, lo + beta) around the median rank; it is
+// summed in rank order (sequential fp32 adds from 0.f) and divided by beta.
+// The window slides up from lo_min = max(0, medrank - beta + 1) while the value
+// it would drop is strictly farther from the median than the one it would take:
+//   lo = lo_min + #{ l in [lo_min, min(medrank, m - beta)) : med - s[l] > s[l + beta] - med }
+// (the predicate is monotone in l: the left distances fall, the right ones rise).
+// This equals the stable argsort of the distances wherever equal distances mean
+// equal values; two different values left of the median whose fp32 distances
+// round to the same number may be taken in the other order.
+// beta is wave-uniform but lo is per lane, and s[l + beta] against s[l] is a
+// register pair at a run-time offset: the lane stages the lower half of its
+// sorted column (every l < medrank <= NP/2 - 1) in LDS laid out [rank][lane]
+// and reads rank j - beta next to register j, so every register index stays a
+// compile-time constant and nothing goes to scratch.  The lower half then lives
+// in LDS alone (the rank sweep reads it back), which frees the registers the
+// search needs.  A lane reads only what it wrote itself: no barrier.  One wave per workgroup keeps the LDS at 16 KiB
+// (NP = 128), 10 workgroups per CU next to the 3 waves/SIMD the registers allow.
+// The rank sweep adds `in ? s[k] : 0.f`: the accumulator starts at +0 and a
+// round-to-nearest sum is never -0 from there, so adding +0 is the identity.
+// NaN as the trimmed mean (mapped to +inf, counted): NaN out when more than
+// m - beta of them (one must be taken) or the median rank itself is one.  A
+// +inf distance never moves the window (the compare is strict), and every LDS
+// rank is clamped, so +-inf columns read in bounds.
+constexpr int WIN_THREADS = 64;
+
+// one v_sub_f32: the compiler pairs two plain subtractions into a packed add,
+// whose aligned register pairs cost copies and spills here
+__device__ __forceinline__ float sub_v(float a, float b) {
+  float d;
+  asm("v_sub_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
+  return d;
+}
+
+template <int NP>
+__global__ __launch_bounds__(WIN_THREADS, 3) void window_mean_kernel(const float* __restrict__ X, int m, int64_t P,
+                                                                      int64_t ldx, int beta,
+                                                                      float* __restrict__ out,
+                                                                      const int32_t* __restrict__ rows,
+                                                                      uint32_t rmax) {
+  constexpr int H = NP / 2;
+  __shared__ float left[H * WIN_THREADS];
+  const int64_t p = (int64_t)blockIdx.x * WIN_THREADS + threadIdx.x;
+  if (p >= P) return;
+  float v[NP];
+  if (rows) {
+#pragma unroll
+    for (int k = 0; k < NP; ++k) v[k] = k < m ? X[(int64_t)min((uint32_t)rows[k], rmax) * ldx + p] : __builtin_huge_valf();
+  } else {
+#pragma unroll
+    for (int k = 0; k < NP; ++k) v[k] = k < m ? X[(int64_t)k * ldx + p] : __builtin_huge_valf();
+  }
+  reg_fence<NP>(v);
+  const int nnan = nan_to_inf<NP>(v);
+  oem_sort<0, NP>(v);
+  reg_fence<NP>(v);
+  __builtin_amdgcn_sched_barrier(0);
+  const int mu = __builtin_amdgcn_readfirstlane(m);
+  const int b = __builtin_amdgcn_readfirstlane(beta);
+  const int med = (mu - 1) / 2;             // <= H - 1
+  const int lo_min = max(0, med - b + 1);
+  const int lmax = min(med, mu - b);        // lo in [lo_min, lmax]
+  float* col = left + threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < H; ++k) col[k * WIN_THREADS] = v[k];
+  // From here the lower half lives in LDS alone (the clobber keeps the loads
+  // below from being forwarded from the registers just stored): 64 registers
+  // free for the rest, which would otherwise spill next to all NP sorted values.
+  asm volatile("" ::: "memory");
+  const float mv = col[med * WIN_THREADS];
+  int lo = lo_min;
+  // the predicate holds on a prefix of the l range, so the last l that passes
+  // gives lo: a select chain (a sum of the 0/1 flags is re-associated into a tree
+  // over NP live flags).  Eight ranks per wave-uniform branch; inside, a rank
+  // outside the range reads +inf from the left (med - inf never passes)
+  // instead of branching.
+#pragma unroll
+  for (int j0 = 0; j0 < NP; j0 += 8) {
+    if (j0 + 8 - b > lo_min && j0 - b < lmax) {
+#pragma unroll
+      for (int j = j0; j < j0 + 8; ++j) {
+        const int l = j - b;                         // wave-uniform
+        const bool ok = l >= lo_min && l < lmax;     // j = l + beta < m: never a padding rank
+        const float a = col[min(max(l, 0), H - 1) * WIN_THREADS];
+        const float r = j < H ? col[j * WIN_THREADS] : v[j];
+        lo = sub_v(mv, ok ? a : __builtin_huge_valf()) > sub_v(r, mv) ? l + 1 : lo;
+      }
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  float acc = 0.f;
+#pragma unroll
+  for (int k = 0; k < NP; ++k) {
+    const bool in = (unsigned)(k - lo) < (unsigned)b;
+    const float x = k < H ? col[k * WIN_THREADS] : v[k];
+    acc = add_rn(acc, in ? x : 0.f);
+  }
+  const bool bad = nnan > mu - b || med >= mu - nnan;
+  out[p] = bad ? __builtin_nanf("") : div_rn(acc, (float)b);
+}
+
+int launch_window(const float* X, int m, int64_t P, int64_t ldx, int beta, float* out, hipStream_t st,
+                  const int32_t* rows, int64_t nrows) {
+  const uint32_t rmax = (uint32_t)(nrows > 0 ? nrows - 1 : 0);  // as launch<>: indices clamped into [0, nrows)
+  const dim3 grid((unsigned)((P + WIN_THREADS - 1) / WIN_THREADS)), block(WIN_THREADS);
+  if (m <= 8)
+    hipLaunchKernelGGL((window_mean_kernel<8>), grid, block, 0, st, X, m, P, ldx, beta, out, rows, rmax);
+  else if (m <= 16)
+    hipLaunchKernelGGL((window_mean_kernel<16>), grid, block, 0, st, X, m, P, ldx, beta, out, rows, rmax);
+  else if (m <= 32)
+    hipLaunchKernelGGL((window_mean_kernel<32>), grid, block, 0, st, X, m, P, ldx, beta, out, rows, rmax);
+  else if (m <= 64)
+    hipLaunchKernelGGL((window_mean_kernel<64>), grid, block, 0, st, X, m, P, ldx, beta, out, rows, rmax);
+  else if (m <= 128)
+    hipLaunchKernelGGL((window_mean_kernel<128>), grid, block, 0, st, X, m, P, ldx, beta, out, rows, rmax);
+  else
+    return FLR_ERR_UNSUPPORTED;
+  return launch_status("window_mean_kernel");
+}
+
 
 // ---- K > 128: one coordinate spread over L = 2 or 4 adjacent lanes ------------
 // Lane g of the group holds clients [128g, 128g+128) (padding +inf).  Each lane
@@ -415,4 +537,12 @@ extern "C" int flr_median_lower_rows(const float* X, int64_t K, int64_t P, int64
   if (K < 1 || m < 1 || m > K || P < 0 || ldx < P || !X || !out || !rows) return FLR_ERR_ARG;
   if (P == 0) return FLR_OK;
   return ostat::launch<1>(X, (int)m, P, ldx, 0, out, as_stream(stream), rows, K);
+}
+
+extern "C" int flr_median_window_mean_rows(const float* X, int64_t K, int64_t P, int64_t ldx, const int32_t* rows,
+                                           int64_t m, int64_t beta, float* out, void* stream) {
+  if (K < 1 || m < 1 || m > K || P < 0 || ldx < P || beta < 1 || beta > m || !X || !out) return FLR_ERR_ARG;
+  if (m > 128) return FLR_ERR_UNSUPPORTED;
+  if (P == 0) return FLR_OK;
+  return ostat::launch_window(X, (int)m, P, ldx, (int)beta, out, as_stream(stream), rows, K);
 }

@@ -4,6 +4,7 @@ Every name of the reference factory is registered and runs on the HIP kernels
 (FLTrust's server update runs on the client-batched trainer).
 """
 from .base_defense import BaseDefense, NoDefense
+from .bulyan import BulyanDefense
 from .krum import KrumDefense, KrumTrimmedMeanDefense, MultiKrumDefense
 from .fltrust import FLTrustDefense
 from .geometric_median import GeometricMedianDefense
@@ -11,7 +12,7 @@ from .norm_based import DPSGDDefense, GradientClippingDefense, NormBoundingDefen
 from .trimmed_mean import MedianDefense, TrimmedMeanDefense
 
 __all__ = [
-    "BaseDefense", "NoDefense", "KrumDefense", "MultiKrumDefense", "KrumTrimmedMeanDefense",
+    "BaseDefense", "NoDefense", "KrumDefense", "MultiKrumDefense", "KrumTrimmedMeanDefense", "BulyanDefense",
     "TrimmedMeanDefense", "MedianDefense", "GeometricMedianDefense",
     "GradientClippingDefense", "NormBoundingDefense", "DPSGDDefense", "FLTrustDefense", "get_defense",
 ]
@@ -30,6 +31,8 @@ _DEFENSES = {
     "fltrust": FLTrustDefense,
     # build extension: Multi-Krum selection then trimmed mean (BASELINE.json configs[4])
     "krum_trimmed_mean": KrumTrimmedMeanDefense,
+    # Bulyan (ICML 2018): iterated Krum selection, then the median-window mean
+    "bulyan": BulyanDefense,
 }
 
 

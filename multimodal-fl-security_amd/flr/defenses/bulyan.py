@@ -1,0 +1,105 @@
+"""Bulyan (El Mhamdi, Guerraoui, Rouault, "The Hidden Vulnerability of
+Distributed Learning in Byzantium", ICML 2018).
+
+n clients, f = num_malicious, theta = n - 2f, beta = theta - 2f; n >= 4f + 3.
+Stage 1 re-runs Krum on the shrinking set: theta times, score the clients
+still alive against each other and move the best one to the selection
+(flr_krum_select_iter: on the device, no host round trip between the picks).
+Stage 2 is coordinate-wise over the theta selected rows: the mean of the beta
+values closest to the lower median (flr_median_window_mean_rows, no gather
+copy of the selection).  Pipeline as KrumDefense: flr_pairwise_l2 -> selection
+-> one pass over the selected rows.  The reference repository has no Bulyan;
+tests/bulyan_ref.py restates the two stages from the oracle's Krum scores.
+"""
+from __future__ import annotations
+
+from typing import Any, Dict, List
+
+import torch
+
+from .. import ops
+from ..matrix import ClientMatrix
+from .base_defense import Updates, as_matrix, source_device
+from .krum import KrumDefense
+
+MAX_ROWS = 128  # rows the window-mean kernel sorts in one lane's registers (include/flr.h)
+
+
+class BulyanDefense(KrumDefense):
+    """Config: num_malicious, pairwise_method (multi_k is ignored: the
+    selection holds theta = n - 2f clients).  selected_clients: the theta
+    picks in pick order; rejected_clients: the rest, ascending;
+    client_scores: the first iteration's Krum scores."""
+
+    def __init__(self, defense_config: Dict[str, Any]):
+        super().__init__(defense_config)
+        self.theta = 0
+        self.beta = 0
+
+    # the window mean reads the selected rows whole: no dead-tap deferral
+    supports_dead_rows = False
+
+    def _sizes(self, n: int) -> None:
+        """theta and beta for n clients; raises before any device work."""
+        f = self.num_malicious
+        if n < 4 * f + 3:
+            raise ValueError(
+                f"Bulyan requires n >= 4f + 3. Got n={n}, f={f}. Need at least {4 * f + 3} clients.")
+        theta = n - 2 * f
+        if theta > MAX_ROWS:
+            raise ValueError(f"Bulyan's median-window mean sorts at most {MAX_ROWS} selected rows "
+                             f"(the 128-row limit). Got theta = n - 2f = {theta} (n={n}, f={f}).")
+        self.theta, self.beta = theta, theta - 2 * f
+
+    def _pick(self) -> torch.Tensor:
+        """The iterated selection on self.distances; returns the int32 picks."""
+        self.scores_device, self.order_device = ops.krum_select_iter(self.distances, self.num_malicious, self.theta)
+        return self.order_device
+
+    def select(self, cm: ClientMatrix) -> torch.Tensor:
+        self._sizes(cm.K)
+        ref = self.pairwise_method == "reference"
+        self.distances = ops.pairwise_l2(cm.X, self.pairwise_method, comm=self.comm,
+                                         tap_blocks=self.tap_blocks if ref else None)
+        self._check_refine_capacity(cm.K)
+        return self._pick()
+
+    def _combine(self, X: torch.Tensor, picked: torch.Tensor) -> torch.Tensor:
+        return ops.median_window_mean(X, self.beta, rows=picked[: self.theta])
+
+    def aggregate_flat(self, cm: ClientMatrix, num_examples: List[int], publish: bool = True) -> torch.Tensor:
+        picked = self.select(cm)
+        if publish:
+            self.publish()
+        return self._combine(cm.X, picked)
+
+    def aggregate_sharded(self, cs, num_examples: List[int], publish: bool = True, events=None) -> torch.Tensor:
+        """Sharded distances, the selection replicated on every rank, then the
+        window mean of this rank's coordinate range."""
+        self._sizes(cs.K)
+        self.distances = self._sharded_distances(cs, events)
+        self._check_refine_capacity(cs.K)
+        self._pick()
+        if publish:
+            self.publish()
+        return self._combine(cs.X, self.order_device)
+
+    def publish(self) -> None:
+        picked = self.order_device.cpu().tolist()
+        self.client_scores = self.scores_device.cpu().tolist()
+        self.selected_clients = picked[: self.theta]
+        self.rejected_clients = picked[self.theta:]
+
+    def aggregate(self, client_updates: Updates, num_examples: List[int]) -> List[torch.Tensor]:
+        # the size rules first: a list input is not even copied to the device
+        self._sizes(client_updates.K if isinstance(client_updates, ClientMatrix) else len(client_updates))
+        cm = as_matrix(client_updates)
+        return cm.unflatten(self.aggregate_flat(cm, num_examples), source_device(client_updates))
+
+    def get_metrics(self) -> Dict[str, Any]:
+        m = super().get_metrics()
+        m.update({"defense_type": "bulyan", "theta": self.theta, "beta": self.beta})
+        return m
+
+    def __repr__(self) -> str:
+        return f"BulyanDefense(f={self.num_malicious})"

@@ -218,11 +218,13 @@ class KrumTrimmedMeanDefense(KrumDefense):
     """"Krum + trimmed-mean" (BASELINE.json configs[4]): the Multi-Krum
     selection (krum.py:149-176, multi_k rows by score) followed by the
     coordinate-wise trimmed mean of the selected rows (trimmed_mean.py:63-90:
-    t = max(1, int(m * trim_ratio)), the median if m - 2t < 1) — the Bulyan
-    composition of the reference's two defenses.  The reference has no such
-    class; its two halves are the reference's own rules, each restated by the
-    oracle.  One extra pass over the selected rows (flr_trimmed_mean_rows),
-    no gather copy of the selection."""
+    t = max(1, int(m * trim_ratio)), the median if m - 2t < 1) — a
+    composition of the reference's two defenses.  It is not Bulyan, which
+    re-runs Krum after every pick and keeps the values closest to the median
+    (defenses/bulyan.py).  The reference has no such class; its two halves are
+    the reference's own rules, each restated by the oracle.  One extra pass
+    over the selected rows (flr_trimmed_mean_rows), no gather copy of the
+    selection."""
 
     def __init__(self, defense_config: Dict[str, Any]):
         super().__init__(defense_config)

@@ -113,6 +113,24 @@ def krum_select(D: torch.Tensor, f: int) -> Tuple[torch.Tensor, torch.Tensor]:
     return scores, order
 
 
+def krum_select_iter(D: torch.Tensor, f: int, theta: int) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Bulyan's iterated Krum selection (flr_krum_select_iter): (scores fp64
+    [K], the first iteration's Krum scores; picked int32 [K], the theta picks
+    in pick order, then the unpicked clients ascending).  All theta iterations
+    are enqueued on the current stream: no host synchronisation."""
+    if not D.is_cuda or D.dtype != torch.float64 or D.dim() != 2 or D.shape[0] != D.shape[1]:
+        raise ValueError("D must be a square float64 device matrix")
+    D = D.contiguous()
+    K = D.shape[0]
+    scores = torch.empty(K, dtype=torch.float64, device=D.device)
+    picked = torch.empty(K, dtype=torch.int32, device=D.device)
+    nbytes = int(_capi.lib().flr_krum_select_iter_workspace(K))
+    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=D.device)
+    _capi.call("flr_krum_select_iter", D.data_ptr(), K, int(f), int(theta), scores.data_ptr(), picked.data_ptr(),
+               ws.data_ptr(), nbytes, _stream(D))
+    return scores, picked
+
+
 def rows_mean(X: torch.Tensor, rows: torch.Tensor, divisor: Optional[int] = None,
               out: Optional[torch.Tensor] = None, dead=None) -> torch.Tensor:
     """Ordered fp32 sum of X[rows] divided by `divisor` (krum.py:182-192).
@@ -191,6 +209,21 @@ def median_lower(X: torch.Tensor, out: Optional[torch.Tensor] = None,
         r = _rows_arg(rows, X.device)
         _capi.call("flr_median_lower_rows", X.data_ptr(), K, P, ldx, r.data_ptr(), r.numel(), out.data_ptr(),
                    _stream(X))
+    return out
+
+
+def median_window_mean(X: torch.Tensor, beta: int, rows: Optional[torch.Tensor] = None,
+                       out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Bulyan's coordinate-wise rule (flr_median_window_mean_rows): the mean
+    of the beta values closest to the lower median, over all K rows or over
+    the row subset `rows` (at most 128 rows either way)."""
+    K, P, ldx = _check_matrix(X)
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=X.device)
+    r = None if rows is None else _rows_arg(rows, X.device)
+    m = K if r is None else r.numel()
+    _capi.call("flr_median_window_mean_rows", X.data_ptr(), K, P, ldx, _ptr(r), m, int(beta), out.data_ptr(),
+               _stream(X))
     return out
 
 
