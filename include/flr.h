@@ -303,7 +303,7 @@ int flr_clip_sgd_step(float* X, const float* G, float* M, int64_t K, int64_t P,
 /* Same step on the parameter-major training layout: block j holds block_numel[j]
  * elements per client at client stride block_client_stride[j] (NULL: the
  * blocks are whole parameters, stride = numel); x/g/m_blocks are host arrays
- * of nblocks device pointers (nblocks <= 768, run as launches of <= 96 blocks).  Client k's element e of block j
+ * of nblocks device pointers (nblocks <= 640, run as launches of <= 80 blocks).  Client k's element e of block j
  * is at ptr_j + k*stride_j + e.  Elements not covered by any block (dead
  * kernel taps, whose gradient is identically zero) are neither read nor
  * updated; with weight_decay == 0 that is exactly the reference's update.
