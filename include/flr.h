@@ -285,6 +285,32 @@ size_t flr_krum_select_iter_workspace(int64_t K);
 int flr_krum_select_iter(const double* D, int64_t K, int64_t f, int64_t theta, double* scores,
                          int32_t* picked, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- a16: colluding model-poisoning attacks (ALIE, IPM) -----------------
+ * ALIE (Baruch, Baruch, Goldberg, NeurIPS 2019) and IPM with a benign mean
+ * (Xie, Koyejo, Gupta, UAI 2019; InnerProductManipulationAttack.poison_update,
+ * src/attacks/model_poisoning.py, the branch next to the sign flip), in place
+ * on the client matrix: rows [0, nmal) are the attackers and are overwritten,
+ * all with the same vector; rows [nmal, K) are benign and only read; columns
+ * [P, ldx) are never touched.  Per coordinate, nb = K - nmal, the benign rows in
+ * ascending row order, every operation a separately rounded fp32 op (no FMA):
+ *   s = sequential adds of x_k from 0.f;           mu = s / (float)nb
+ *   q = sequential adds of (x_k - mu)*(x_k - mu) from 0.f
+ *   sigma = sqrt(q / (float)nb)     (population deviation, correctly rounded)
+ *   FLR_COLLUDE_ALIE: out = mu - param * sigma;  FLR_COLLUDE_IPM: out = -(param * mu)
+ * so a torch CPU loop over the rows gives the same bits.  NaN and inf follow
+ * IEEE: a NaN in a benign row makes that coordinate of the attackers' rows NaN
+ * and no other.  mean_out / std_out: optional device fp32 [P] (NULL: not
+ * written), mu and sigma; in IPM mode sigma is computed only for std_out.
+ * Coordinate-wise: any column range of X (same ldx) gives that range of the
+ * whole-matrix result.  Any K; no workspace.
+ * FLR_ERR_ARG: null X, K < 2, nmal < 1, nmal >= K, P < 1, ldx < P, mode outside
+ * {0, 1}; nothing is written then. */
+#define FLR_COLLUDE_ALIE 0   /* out = mu - param * sigma   (param = z)       */
+#define FLR_COLLUDE_IPM  1   /* out = -(param * mu)        (param = epsilon) */
+int flr_collude_rows(float* X, int64_t K, int64_t P, int64_t ldx, int64_t nmal,
+                     int mode, float param, float* mean_out, float* std_out,
+                     void* stream);
+
 /* ---- a6 + a7: fused gradient clip + SGD-momentum step -----------------
  * Replaces, for every client row at once, clip_grad_norm_(params, max_norm)
  * + torch.optim.SGD(lr, momentum, weight_decay).step()

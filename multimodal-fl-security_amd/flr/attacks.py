@@ -12,19 +12,66 @@
   and the label replaced by target_class (BackdoorDataset, :13-60).
   Applied here to a malicious client's resident synthetic batches before the
   round (data generation, not timed).
+* ALIE — "A Little Is Enough" (Baruch, Baruch, Goldberg, NeurIPS 2019): the
+  f colluding attackers know the benign updates and all submit mu - z * sigma
+  per coordinate (the benign mean and population standard deviation), z from
+  the normal quantile that keeps them inside the benign spread (alie_z).  Not
+  in the reference; the attack Krum, the trimmed mean and Bulyan are judged by.
+* IPM with a benign mean — "Fall of Empires" (Xie, Koyejo, Gupta, UAI 2019),
+  the other branch of InnerProductManipulationAttack.poison_update
+  (src/attacks/model_poisoning.py, next to the sign flip's -param): every
+  attacker submits -epsilon * mu.
+  Both are one pass of flr_collude_rows over the exchanged client matrix
+  (attackers = rows 0..f-1, overwritten in place), applied by the engine
+  between the exchange and the defense.
 """
 from __future__ import annotations
 
-from typing import List, Sequence, Tuple
+import statistics
+from typing import List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
+
+from . import ops
 
 
 def sign_flip_(X: torch.Tensor, rows: Sequence[int]) -> None:
     """In place: X[r] = -X[r] for the malicious rows."""
     for r in rows:
         X[r].neg_()
+
+
+def alie_z(n: int, f: int) -> float:
+    """ALIE's z for n clients of which f collude: s = n // 2 + 1 - f benign
+    clients must sit farther from the mean than the attackers for them to be in
+    the majority, so z = Phi^-1((n - s) / n) (the paper's z_max)."""
+    n, f = int(n), int(f)
+    s = n // 2 + 1 - f
+    if f < 1 or not 1 <= s <= n - 1:
+        raise ValueError(f"alie_z needs 1 <= f and 1 <= n // 2 + 1 - f <= n - 1 (got n = {n}, f = {f})")
+    return statistics.NormalDist().inv_cdf((n - s) / n)
+
+
+def _attacked_matrix(X, f: int) -> torch.Tensor:
+    """The [K, P] view of a ClientMatrix (or the tensor itself), f checked."""
+    M = X if isinstance(X, torch.Tensor) else X.X
+    if not 1 <= f < M.shape[0]:
+        raise ValueError(f"a colluding attack needs 1 <= f < K (got f = {f}, K = {M.shape[0]})")
+    return M
+
+
+def alie_(X, f: int, z: Optional[float] = None) -> None:
+    """In place on a float32 device matrix or a ClientMatrix: rows 0..f-1 <-
+    mu - z * sigma of rows f..K-1 (z None: alie_z(K, f))."""
+    M = _attacked_matrix(X, f)
+    ops.collude_rows(M, f, ops.COLLUDE_ALIE, alie_z(M.shape[0], f) if z is None else z)
+
+
+def ipm_(X, f: int, epsilon: float = 0.5) -> None:
+    """In place on a float32 device matrix or a ClientMatrix: rows 0..f-1 <-
+    -epsilon * mu, mu the mean of rows f..K-1."""
+    ops.collude_rows(_attacked_matrix(X, f), f, ops.COLLUDE_IPM, epsilon)
 
 
 class Backdoor:

@@ -227,6 +227,25 @@ def median_window_mean(X: torch.Tensor, beta: int, rows: Optional[torch.Tensor] 
     return out
 
 
+COLLUDE_ALIE, COLLUDE_IPM = 0, 1  # FLR_COLLUDE_*
+
+
+def collude_rows(X: torch.Tensor, nmal: int, mode: int, param: float, mean_out: Optional[torch.Tensor] = None,
+                 std_out: Optional[torch.Tensor] = None) -> None:
+    """The colluding attacks in place (flr_collude_rows): rows [0, nmal) of X
+    <- mu - param * sigma (COLLUDE_ALIE) or -(param * mu) (COLLUDE_IPM), mu and
+    sigma the benign rows' [nmal, K) coordinate-wise mean and population
+    deviation; mean_out / std_out: optional float32 [P] device vectors that
+    receive them."""
+    K, P, ldx = _check_matrix(X)
+    for name, t in (("mean_out", mean_out), ("std_out", std_out)):
+        if t is not None and (t.device != X.device or t.dtype != torch.float32 or not t.is_contiguous()
+                              or t.numel() != P):
+            raise ValueError(f"{name} must be a contiguous float32 [{P}] vector on {X.device}")
+    _capi.call("flr_collude_rows", X.data_ptr(), K, P, ldx, int(nmal), int(mode), float(param), _ptr(mean_out),
+               _ptr(std_out), _stream(X))
+
+
 def row_norms(X: torch.Tensor, center: Optional[torch.Tensor] = None, kind: str = "l2") -> torch.Tensor:
     """float64 [K]: ||X_i - center|| per row (l2 or linf); fp32 differences,
     fp64 accumulation in a fixed order (differential_privacy.py:223-236,

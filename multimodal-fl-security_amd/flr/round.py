@@ -29,7 +29,7 @@ import torch
 from . import _capi
 from . import dist as fdist
 from . import ops
-from .attacks import Backdoor, poison_batches_
+from .attacks import Backdoor, alie_z, poison_batches_
 from .defenses import get_defense
 from .defenses.krum import DeadTaps
 from .matrix import ClientMatrix
@@ -38,13 +38,18 @@ from .models.multimodal import ModelSpec, model_class, param_layout
 from .train import ClientBatchTrainer, TrainConfig, make_dropout_masks, synthetic_batches
 
 
+ATTACKS = ("sign_flip", "backdoor", "none", "alie", "ipm")
+
+
 @dataclass
 class RoundConfig:
     num_clients: int = 128
     batch: int = 32                      # run_experiments.py:40
     defense: str = "krum"
     defense_cfg: Dict = field(default_factory=dict)
-    attack: str = "sign_flip"            # "sign_flip" (model_poisoning.py:274-276) | "backdoor" | "none"
+    # "sign_flip" (model_poisoning.py:274-276) | "backdoor" | "none" | "alie" | "ipm" (the colluding attacks of
+    # flr.attacks: one flr_collude_rows pass between the exchange and the defense)
+    attack: str = "sign_flip"
     num_attackers: int = 25              # f = int(0.2 K), clients 0..f-1 (experiment_matrix.py:67-68)
     seed: int = 42                       # run_experiments.py:43
     exchange: str = "auto"               # "alltoall" | "allgather" | "auto" (alltoall when the defense shards)
@@ -57,6 +62,7 @@ class RoundConfig:
     # the defense's next collective would hang the round instead of failing it;
     # False keeps device errors loud at world 1 too
     fallback_device_errors: bool = True
+    attack_cfg: Dict = field(default_factory=dict)  # "z" (alie; default alie_z(K, f)), "epsilon" (ipm; default 0.5)
 
 
 def initial_global(spec: ModelSpec, seed: int, device) -> torch.Tensor:
@@ -69,6 +75,19 @@ def initial_global(spec: ModelSpec, seed: int, device) -> torch.Tensor:
 class RoundEngine:
     def __init__(self, spec: ModelSpec, rcfg: RoundConfig, tcfg: TrainConfig = TrainConfig(), device="cuda",
                  rank: int = 0, world: int = 1):
+        if rcfg.attack not in ATTACKS:  # a typo must not run as an unattacked round
+            raise ValueError(f"unknown attack {rcfg.attack!r} (one of {', '.join(ATTACKS)})")
+        # the colluding attacks: (mode, param) of the one flr_collude_rows call per round
+        self._collude = None
+        if rcfg.attack in ("alie", "ipm"):
+            K, f = rcfg.num_clients, rcfg.num_attackers
+            if not 1 <= f < K:
+                raise ValueError(f"attack {rcfg.attack!r} needs 1 <= num_attackers < num_clients (got {f}, {K})")
+            if rcfg.attack == "alie":
+                z = rcfg.attack_cfg.get("z")
+                self._collude = (ops.COLLUDE_ALIE, float(alie_z(K, f) if z is None else z))
+            else:
+                self._collude = (ops.COLLUDE_IPM, float(rcfg.attack_cfg.get("epsilon", 0.5)))
         defer = os.environ.get("FLR_DEFER_DEAD", "2")
         if defer == "1":  # loud: an old A/B script must not report numbers for another mode
             raise ValueError("FLR_DEFER_DEAD=1 (the dead-tap fill on a side stream beside the Krum chains) was "
@@ -152,10 +171,12 @@ class RoundEngine:
         # mean too (flr_rows_mean_dead): C3 15.65-15.73 -> 15.94-15.99 rounds/s,
         # the same bits (profiles/r6_dead/); materialize() writes them for any
         # other reader of X (the full / slice / client_matrix properties call
-        # it); =0: written last in the training phase
+        # it); =0: written last in the training phase.  Not armed under the
+        # colluding attacks (alie, ipm): their pass reads the benign rows and
+        # writes the attackers' rows whole, before the defense
         self._dead: Optional[DeadTaps] = None
         self._x_stale = False  # set where run_round arms the deferral, cleared by materialize() alone
-        if (self.train_order and world == 1 and self.defense.__dict__.get("tap_blocks")
+        if (self.train_order and world == 1 and self._collude is None and self.defense.__dict__.get("tap_blocks")
                 and getattr(self.defense, "supports_dead_rows", False)
                 and hasattr(self.trainer, "fill_dead") and defer == "2"):
             masks = self._dead_masks(self.defense.tap_blocks)
@@ -326,6 +347,7 @@ class RoundEngine:
         self.fallback_error = None
         if self.exchange == "alltoall":
             cs = self._slice = self.xchg.exchange(self.trainer.X.data)
+            self._apply_collusion(cs.X)  # coordinate-wise: this rank's slice needs no other
             try:
                 part = self.defense.aggregate_sharded(cs, self.num_examples, **kw)
             except Exception as e:  # noqa: BLE001 - the reference catches any exception
@@ -333,6 +355,7 @@ class RoundEngine:
             cs.gather_vector(part, self.gtrain if self.train_order else self.global_flat)
             return self._publish()
         fdist.allgather_rows(self.trainer.X.data, self._full.data)
+        self._apply_collusion(self._full.X)  # replicated: every rank computes the same bits
         if self._wants_global:  # FLTrust: the server update starts from this round's global model
             kw["global_flat"] = self.global_flat.clone()  # global_flat is overwritten below
         try:
@@ -340,6 +363,14 @@ class RoundEngine:
         except Exception as e:  # noqa: BLE001
             agg = self._fallback(e, self._full.X)
         return self._publish(agg)
+
+    def _apply_collusion(self, X: torch.Tensor) -> None:
+        """attack "alie" / "ipm": the attackers (clients 0..f-1, who trained
+        honestly) replace their rows of the exchanged matrix by the colluding
+        vector, computed from the benign rows — after the exchange, before the
+        defense, outside the captured training graph."""
+        if self._collude is not None:
+            ops.collude_rows(X, self.rcfg.num_attackers, *self._collude)
 
     def _fallback(self, err: Exception, X: torch.Tensor) -> torch.Tensor:
         """robust_server.py:120-122: a failing defense falls back to FedAvg
