@@ -311,6 +311,49 @@ int flr_collude_rows(float* X, int64_t K, int64_t P, int64_t ldx, int64_t nmal,
                      int mode, float param, float* mean_out, float* std_out,
                      void* stream);
 
+/* ---- centered clipping (Karimireddy, He, Jaggi, ICML 2021) ---------------
+ * "Learning from History for Byzantine Robust Optimization": from the previous
+ * global model v0, iters times
+ *   v <- v + (1/K) * sum_i (x_i - v) * min(1, tau / ||x_i - v||)
+ * so one call moves the aggregate by at most iters * tau however the attackers
+ * collude.  No reference counterpart.  The whole loop is enqueued on the stream,
+ * no host synchronisation.  Iteration l = 0 .. iters-1, v_0 = v0:
+ *   1. distances (flr_row_norms, type 0, center v_l): d_i = ||x_i - v_l||, fp32
+ *      differences, squares summed in fp64 in a fixed order, fp64 square root.
+ *   2. scales, fp32 throughout: d32_i = (float)d_i (round to nearest);
+ *        t = tau when tau > 0; when tau == 0 (adaptive mode) t = the lower median
+ *            of the K values d32, sort(d32)[(K-1)/2] with NaN sorted last (numpy's
+ *            order): at most half the rows are clipped;
+ *        s_i = 0 if d32_i is NaN;  else t / d32_i if d32_i > t (one correctly
+ *              rounded division; +inf gives 0);  else 1.
+ *      A median t of NaN compares false with everything (every non-NaN row keeps
+ *      s_i = 1); a median t of 0 gives every row at a positive distance s_i = 0.
+ *   3. step, per coordinate, the rows in ascending order, every operation a
+ *      separately rounded fp32 op (no FMA):
+ *        acc = +0.f
+ *        for i in 0..K-1:  if s_i != 0:  acc = acc + (x_i - v) * s_i
+ *        v' = v + acc / (float)K
+ *      A row with s_i == 0 is skipped, not multiplied: a client holding a NaN or
+ *      an inf (distance NaN or +inf) leaves the aggregate finite, as Krum ranks
+ *      such a client last.  The divisor stays K.
+ * so a torch CPU loop over the rows, given the distances, gives the same bits.
+ * out: device fp32 [P], v_iters; must not be v0 (the iterates alternate between
+ * out and a P-vector of the workspace; v0 is only read).  Optional device
+ * outputs (NULL: not written): norms_out fp64 [iters][K], the d_i; scales_out
+ * fp32 [iters][K], the s_i; tau_out fp32 [iters], the t used.  Columns [P, ldx)
+ * of X are never touched.  Bytes moved: 2 * iters * K * P * 4 (the distance pass
+ * and the step each read X once).
+ * FLR_ERR_ARG: null X, v0 or out; K < 1; P < 1; ldx < P; iters < 1; tau < 0 or
+ * NaN; out == v0.  FLR_ERR_WORKSPACE: workspace null, smaller than
+ * flr_centered_clip_workspace(K, P) (0 for K < 1 or P < 1) or not 256-byte
+ * aligned.  FLR_ERR_UNSUPPORTED: K > 4096 (the scales kernel is one workgroup;
+ * flr_weighted_rows' row limit).  Nothing is written on an error. */
+size_t flr_centered_clip_workspace(int64_t K, int64_t P);
+int flr_centered_clip(const float* X, int64_t K, int64_t P, int64_t ldx,
+                      const float* v0, float tau, int64_t iters, float* out,
+                      double* norms_out, float* scales_out, float* tau_out,
+                      void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- a6 + a7: fused gradient clip + SGD-momentum step -----------------
  * Replaces, for every client row at once, clip_grad_norm_(params, max_norm)
  * + torch.optim.SGD(lr, momentum, weight_decay).step()

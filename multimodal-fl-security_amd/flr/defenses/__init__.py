@@ -5,6 +5,7 @@ Every name of the reference factory is registered and runs on the HIP kernels
 """
 from .base_defense import BaseDefense, NoDefense
 from .bulyan import BulyanDefense
+from .centered_clipping import CenteredClippingDefense
 from .krum import KrumDefense, KrumTrimmedMeanDefense, MultiKrumDefense
 from .fltrust import FLTrustDefense
 from .geometric_median import GeometricMedianDefense
@@ -14,7 +15,8 @@ from .trimmed_mean import MedianDefense, TrimmedMeanDefense
 __all__ = [
     "BaseDefense", "NoDefense", "KrumDefense", "MultiKrumDefense", "KrumTrimmedMeanDefense", "BulyanDefense",
     "TrimmedMeanDefense", "MedianDefense", "GeometricMedianDefense",
-    "GradientClippingDefense", "NormBoundingDefense", "DPSGDDefense", "FLTrustDefense", "get_defense",
+    "GradientClippingDefense", "NormBoundingDefense", "DPSGDDefense", "FLTrustDefense", "CenteredClippingDefense",
+    "get_defense",
 ]
 
 _DEFENSES = {
@@ -33,6 +35,8 @@ _DEFENSES = {
     "krum_trimmed_mean": KrumTrimmedMeanDefense,
     # Bulyan (ICML 2018): iterated Krum selection, then the median-window mean
     "bulyan": BulyanDefense,
+    # centered clipping (ICML 2021): iterated clipped mean around the previous global model
+    "centered_clipping": CenteredClippingDefense,
 }
 
 

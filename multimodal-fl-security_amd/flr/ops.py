@@ -246,6 +246,41 @@ def collude_rows(X: torch.Tensor, nmal: int, mode: int, param: float, mean_out: 
                _ptr(std_out), _stream(X))
 
 
+def centered_clip(X: torch.Tensor, v0: torch.Tensor, tau: float, iters: int, out: Optional[torch.Tensor] = None,
+                  diagnostics: bool = False):
+    """Centered clipping (flr_centered_clip): from v0, iters times
+    v <- v + (1/K) * sum_i (x_i - v) * min(1, tau / ||x_i - v||); tau = 0: the
+    threshold of each iteration is the lower median of its K distances.  All
+    iterations are enqueued on the current stream: no host synchronisation.
+    Returns out (float32 [P]; must not be v0), or with diagnostics (out, norms
+    float64 [iters, K], scales float32 [iters, K], taus float32 [iters]) as
+    device tensors."""
+    K, P, ldx = _check_matrix(X)
+    for name, t in (("v0", v0), ("out", out)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.device != X.device or t.dtype != torch.float32
+                              or not t.is_contiguous() or t.numel() != P):
+            raise ValueError(f"{name} must be a contiguous float32 [{P}] vector on {X.device}")
+    if v0 is None:
+        raise ValueError("v0 must be a float32 device vector of length P")
+    tau, iters = float(tau), int(iters)
+    if not tau >= 0.0:
+        raise ValueError(f"tau must be >= 0 (0: the median of the distances), got {tau}")
+    if iters < 1:
+        raise ValueError(f"iters must be >= 1, got {iters}")
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=X.device)
+    norms = scales = taus = None
+    if diagnostics:
+        norms = torch.empty((iters, K), dtype=torch.float64, device=X.device)
+        scales = torch.empty((iters, K), dtype=torch.float32, device=X.device)
+        taus = torch.empty(iters, dtype=torch.float32, device=X.device)
+    nbytes = int(_capi.lib().flr_centered_clip_workspace(K, P))
+    ws, wp = _ws(nbytes, X.device)
+    _capi.call("flr_centered_clip", X.data_ptr(), K, P, ldx, v0.data_ptr(), tau, iters, out.data_ptr(), _ptr(norms),
+               _ptr(scales), _ptr(taus), wp, nbytes, _stream(X))
+    return (out, norms, scales, taus) if diagnostics else out
+
+
 def row_norms(X: torch.Tensor, center: Optional[torch.Tensor] = None, kind: str = "l2") -> torch.Tensor:
     """float64 [K]: ||X_i - center|| per row (l2 or linf); fp32 differences,
     fp64 accumulation in a fixed order (differential_privacy.py:223-236,
