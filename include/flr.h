@@ -311,6 +311,77 @@ int flr_collude_rows(float* X, int64_t K, int64_t P, int64_t ldx, int64_t nmal,
                      int mode, float param, float* mean_out, float* std_out,
                      void* stream);
 
+/* ---- Min-Max / Min-Sum colluding attacks (Shejwalkar, Houmansadr, NDSS 2021)
+ * "Manipulating the Byzantine": aggregator-agnostic; no reference counterpart.
+ * In place on the client matrix, as flr_collude_rows: rows [0, nmal) are the
+ * attackers and are overwritten, all with the same vector m = mu + gamma * p;
+ * rows [nmal, K) are benign and only read, nb = K - nmal; columns [P, ldx) are
+ * never touched.  The rows are model weights; `global` (device fp32 [P]) is the
+ * model the clients started from.  gamma is the largest strength >= 0 with
+ *   FLR_MINMAX_MAX:  max_i ||m - x_i||^2 <= R2 = max_ij ||x_i - x_j||^2
+ *   FLR_MINMAX_SUM:  sum_i ||m - x_i||^2 <= S  = max_i sum_j ||x_i - x_j||^2
+ * over the benign rows, solved in closed form (the paper halves an interval,
+ * one pass over the matrix per probe).  The whole call is enqueued on the
+ * stream, no host synchronisation.  Stages, op for op:
+ *   1. mu, sigma: flr_collude_rows' mean_out / std_out (its arithmetic, its
+ *      bits), no row written.
+ *   2. D: flr_pairwise_l2 (the Gram engine) on the benign rows, nb x nb fp64
+ *      holding float32-rounded distances.  R2 and S are DEFINED from it, in fp64:
+ *        R2 = max_ij D[i][j]*D[i][j];   S = max_i (sequential sum over j = 0..nb-1
+ *        of D[i][j]*D[i][j], from 0.0);   a NaN term makes the maximum NaN.
+ *   3. the perturbation, per coordinate, fp32:
+ *        FLR_PERTURB_STD:   p = -sigma
+ *        FLR_PERTURB_SIGN:  t = mu - g;  p = -sign(t), sign(0) = 0, sign(NaN) = NaN
+ *        FLR_PERTURB_UNIT:  p = -(mu - g), NOT normalised: only p's direction
+ *                           matters for the rows, and gamma is relative to this
+ *                           p — gamma * sqrt(c) is the paper's unit-vector gamma.
+ *      and the statistics, d_ik = fl32(mu_k - x_ik):
+ *        a_i = sum_k d_ik*d_ik    b_i = sum_k p_k*d_ik    c = sum_k p_k*p_k
+ *      each product exact in fp64, each sum a fixed-order fp64 sum whose order is
+ *      the kernel's own (a function of K, P, ldx and the pointers' 16-B alignment
+ *      alone: run-to-run identical bits, no float atomics), so they are accurate
+ *      to about P * 2^-53 relative, not bit-defined.  X is read once for both.
+ *   4. gamma, fp64, every operation correctly rounded, in the order written
+ *      (bit-defined given a, b, c, R2, S):
+ *        any of a_i, b_i, c, R2, S NaN:   gamma = NaN
+ *        else c == 0:                     gamma = 0      (e.g. nb = 1 with STD)
+ *        else FLR_MINMAX_MAX:  h_i = R2 - a_i, h_i < 0 replaced by 0 (a_i <= R2
+ *                                 mathematically: the mean is in the benign hull)
+ *                              gamma_i = (sqrt(b_i*b_i + c*h_i) - b_i) / c
+ *                              gamma = min_i gamma_i; a NaN gamma_i (inf - inf in
+ *                                 h_i) makes it NaN (numpy's min)
+ *        else FLR_MINMAX_SUM:  A = sequential sum of a_i, Bs = of b_i, from 0.0
+ *                              h = S - A, h < 0 replaced by 0;  n = (double)nb * c
+ *                              gamma = (sqrt(Bs*Bs + n*h) - Bs) / n
+ *   5. the rows (bit-defined given mu, p, gamma), two separately rounded fp32
+ *      ops as in flr_collude_rows:   out = mu + (float)gamma * p
+ *      gamma NaN: nothing is written — one NaN in a benign row does not become
+ *      NaN in every attacker row; the returned gamma says so.  (The Gram
+ *      engine's all-NaN marker at nb > 128, see flr_pairwise_l2, ends the same way.)
+ * gamma_out: optional device fp64 scalar.  stats_out: optional device fp64
+ * [2*nb + 4]: a_i [nb], b_i [nb], c, R2, S, the bound used (R2 or S).
+ * Workspace: flr_minmax_workspace(K, P, nmal) bytes (0 for arguments the call
+ * rejects), 256-byte aligned; it includes flr_pairwise_l2's.  After the call
+ * its first P floats hold mu and the P floats at byte offset
+ * (4*P + 255) / 256 * 256 hold sigma.
+ * Bytes moved: 3 * nb * P * 4 read (mean, Gram, statistics) + nmal * P * 4 written.
+ * FLR_ERR_ARG: null X, K < 2, nmal < 1, nmal >= K, P < 1, ldx < P, objective or
+ * perturb outside their values, global NULL unless FLR_PERTURB_STD.
+ * FLR_ERR_WORKSPACE: workspace null, too small or not 256-byte aligned.
+ * FLR_ERR_UNSUPPORTED: nb > 1024, flr_pairwise_l2's row limit (the one-workgroup
+ * solve alone would carry 4096).  Nothing is written on an error.
+ * nb = 1 is legal: R2 = S = 0, a_0 = 0, gamma = 0, the rows become mu. */
+#define FLR_MINMAX_MAX 0
+#define FLR_MINMAX_SUM 1
+#define FLR_PERTURB_STD 0
+#define FLR_PERTURB_SIGN 1
+#define FLR_PERTURB_UNIT 2
+size_t flr_minmax_workspace(int64_t K, int64_t P, int64_t nmal);
+int flr_minmax_rows(float* X, int64_t K, int64_t P, int64_t ldx, int64_t nmal,
+                    int objective, int perturb, const float* global,
+                    double* gamma_out, double* stats_out, void* workspace,
+                    size_t workspace_bytes, void* stream);
+
 /* ---- centered clipping (Karimireddy, He, Jaggi, ICML 2021) ---------------
  * "Learning from History for Byzantine Robust Optimization": from the previous
  * global model v0, iters times

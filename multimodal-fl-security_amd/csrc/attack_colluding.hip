@@ -41,12 +41,15 @@ __device__ __forceinline__ void reg_fence(float* v) {
 
 // mu, sigma -> the attackers' rows and the optional outputs.  Every load of the
 // column is done by now: the rows written here are never among the rows read.
+// mode STATS_ONLY (attack_minmax.hip's first stage): the outputs alone.
 __device__ __forceinline__ void finish(float* __restrict__ X, int64_t p, int64_t ldx, int64_t nmal, int mode,
                                        float param, float mu, float sigma, float* __restrict__ mean_out,
                                        float* __restrict__ std_out) {
-  const float a = mode == FLR_COLLUDE_ALIE ? sub_rn(mu, mul_rn(param, sigma)) : -mul_rn(param, mu);
-  float* dst = X + p;
-  for (int64_t r = 0; r < nmal; ++r) dst[r * ldx] = a;
+  if (mode != STATS_ONLY) {  // wave-uniform
+    const float a = mode == FLR_COLLUDE_ALIE ? sub_rn(mu, mul_rn(param, sigma)) : -mul_rn(param, mu);
+    float* dst = X + p;
+    for (int64_t r = 0; r < nmal; ++r) dst[r * ldx] = a;
+  }
   if (mean_out) mean_out[p] = mu;
   if (std_out) std_out[p] = sigma;
 }

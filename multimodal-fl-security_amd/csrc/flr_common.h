@@ -30,6 +30,15 @@ inline int launch_status(const char* where) {
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// attack_colluding.hip: flr_collude_rows' launch.  mode STATS_ONLY writes no row
+// of X, only mean_out / std_out — the same kernels, so the same bits
+// (attack_minmax.hip's first stage).
+namespace collude {
+constexpr int STATS_ONLY = -1;
+int launch(float* X, int64_t K, int64_t P, int64_t ldx, int64_t nmal, int mode, float param, float* mean_out,
+           float* std_out, hipStream_t st);
+}  // namespace collude
+
 __host__ __device__ constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 
 // fp32 add/mul/div with no contraction (the reference computes each op as a

@@ -76,6 +76,9 @@ SIGNATURES = {
     "flr_krum_select_iter": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _size_t, _c_void_p]),
     "flr_collude_rows": (_int, [_c_void_p, _i64, _i64, _i64, _i64, _int, ctypes.c_float, _c_void_p, _c_void_p,
                                 _c_void_p]),
+    "flr_minmax_workspace": (_size_t, [_i64, _i64, _i64]),
+    "flr_minmax_rows": (_int, [_c_void_p, _i64, _i64, _i64, _i64, _int, _int, _c_void_p, _c_void_p, _c_void_p,
+                               _c_void_p, _size_t, _c_void_p]),
     "flr_centered_clip_workspace": (_size_t, [_i64, _i64]),
     "flr_centered_clip": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, ctypes.c_float, _i64, _c_void_p, _c_void_p,
                                  _c_void_p, _c_void_p, _c_void_p, _size_t, _c_void_p]),

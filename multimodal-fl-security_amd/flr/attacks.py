@@ -24,6 +24,14 @@
   Both are one pass of flr_collude_rows over the exchanged client matrix
   (attackers = rows 0..f-1, overwritten in place), applied by the engine
   between the exchange and the defense.
+* Min-Max / Min-Sum — "Manipulating the Byzantine" (Shejwalkar, Houmansadr,
+  NDSS 2021): every attacker submits mu + gamma * p, p a perturbation direction
+  (-sigma, -sign(mu - g) or -(mu - g)), gamma the largest strength that keeps
+  the vector no further from the benign rows than they are from each other
+  (the maximum distance, or the sum of squared distances).  Aggregator-
+  agnostic, the strength computed from the round's own matrix instead of
+  guessed per defense; not in the reference.  One flr_minmax_rows call in the
+  same slot (min_max_, min_sum_); it needs whole rows.
 """
 from __future__ import annotations
 
@@ -72,6 +80,37 @@ def ipm_(X, f: int, epsilon: float = 0.5) -> None:
     """In place on a float32 device matrix or a ClientMatrix: rows 0..f-1 <-
     -epsilon * mu, mu the mean of rows f..K-1."""
     ops.collude_rows(_attacked_matrix(X, f), f, ops.COLLUDE_IPM, epsilon)
+
+
+PERTURBATIONS = {"std": ops.PERTURB_STD, "sign": ops.PERTURB_SIGN, "unit": ops.PERTURB_UNIT}
+
+
+def _minmax(X, f: int, objective: int, perturb: str, global_flat) -> torch.Tensor:
+    M = _attacked_matrix(X, f)
+    if perturb not in PERTURBATIONS:
+        raise ValueError(f"unknown perturbation {perturb!r} (one of {', '.join(PERTURBATIONS)})")
+    if perturb != "std" and global_flat is None:
+        raise ValueError(f"perturbation {perturb!r} needs global_flat, the model the clients started from")
+    return ops.minmax_rows(M, f, objective, PERTURBATIONS[perturb], global_flat)
+
+
+def min_max_(X, f: int, perturb: str = "std", global_flat: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """In place on a float32 device matrix or a ClientMatrix: rows 0..f-1 <-
+    mu + gamma * p, gamma the largest strength with max_i ||m - x_i|| no larger
+    than the largest distance between two benign rows f..K-1.  perturb: "std"
+    (p = -sigma), "sign" (p = -sign(mu - g)) or "unit" (p = -(mu - g), not
+    normalised; gamma * ||p|| is the paper's unit-vector gamma), g =
+    global_flat.  Returns gamma, a float64 device scalar (NaN: a benign row
+    held a NaN and the rows were left as they were) — unlike alie_ / ipm_ the
+    strength is a result here."""
+    return _minmax(X, f, ops.MINMAX_MAX, perturb, global_flat)
+
+
+def min_sum_(X, f: int, perturb: str = "std", global_flat: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """As min_max_, gamma the largest strength with sum_i ||m - x_i||^2 no
+    larger than the largest sum of squared distances from one benign row to the
+    others."""
+    return _minmax(X, f, ops.MINMAX_SUM, perturb, global_flat)
 
 
 class Backdoor:

@@ -246,6 +246,44 @@ def collude_rows(X: torch.Tensor, nmal: int, mode: int, param: float, mean_out: 
                _ptr(std_out), _stream(X))
 
 
+MINMAX_MAX, MINMAX_SUM = 0, 1                    # FLR_MINMAX_*
+PERTURB_STD, PERTURB_SIGN, PERTURB_UNIT = 0, 1, 2  # FLR_PERTURB_*
+
+
+def minmax_rows(X: torch.Tensor, nmal: int, objective: int, perturb: int, global_flat: Optional[torch.Tensor] = None,
+                diagnostics: bool = False):
+    """The Min-Max / Min-Sum attacks in place (flr_minmax_rows): rows [0, nmal)
+    of X <- mu + gamma * p, mu the benign rows' [nmal, K) mean, p = -sigma
+    (PERTURB_STD), -sign(mu - g) (PERTURB_SIGN) or -(mu - g) (PERTURB_UNIT, not
+    normalised: gamma is relative to this p), g = global_flat, gamma the largest
+    strength that keeps the vector within the benign rows' largest mutual
+    distance (MINMAX_MAX) or largest distance sum (MINMAX_SUM).  The whole call
+    is enqueued on the current stream: no host synchronisation.  Returns gamma
+    (float64 device scalar; NaN: a statistic was NaN and no row was written), or
+    with diagnostics (gamma, stats float64 [2 * nb + 4] — a_i, b_i, c, R2, S,
+    the bound used —, mu float32 [P], sigma float32 [P]) as device tensors."""
+    K, P, ldx = _check_matrix(X)
+    if global_flat is not None and (not isinstance(global_flat, torch.Tensor) or global_flat.device != X.device
+                                    or global_flat.dtype != torch.float32 or not global_flat.is_contiguous()
+                                    or global_flat.numel() != P):
+        raise ValueError(f"global_flat must be a contiguous float32 [{P}] vector on {X.device}")
+    nmal = int(nmal)
+    gamma = torch.empty((), dtype=torch.float64, device=X.device)
+    stats = None
+    if diagnostics:
+        stats = torch.empty(2 * max(K - nmal, 0) + 4, dtype=torch.float64, device=X.device)
+    nbytes = int(_capi.lib().flr_minmax_workspace(K, P, nmal))
+    ws, wp = _ws(nbytes, X.device)
+    _capi.call("flr_minmax_rows", X.data_ptr(), K, P, ldx, nmal, int(objective), int(perturb), _ptr(global_flat),
+               gamma.data_ptr(), _ptr(stats), wp, nbytes, _stream(X))
+    if not diagnostics:
+        return gamma
+    off = wp - ws.data_ptr()
+    sig = off + (4 * P + 255) // 256 * 256
+    return (gamma, stats, ws[off:off + 4 * P].view(torch.float32).clone(),
+            ws[sig:sig + 4 * P].view(torch.float32).clone())
+
+
 def centered_clip(X: torch.Tensor, v0: torch.Tensor, tau: float, iters: int, out: Optional[torch.Tensor] = None,
                   diagnostics: bool = False):
     """Centered clipping (flr_centered_clip): from v0, iters times

@@ -29,7 +29,7 @@ import torch
 from . import _capi
 from . import dist as fdist
 from . import ops
-from .attacks import Backdoor, alie_z, poison_batches_
+from .attacks import PERTURBATIONS, Backdoor, alie_z, poison_batches_
 from .defenses import get_defense
 from .defenses.krum import DeadTaps
 from .matrix import ClientMatrix
@@ -38,7 +38,7 @@ from .models.multimodal import ModelSpec, model_class, param_layout
 from .train import ClientBatchTrainer, TrainConfig, make_dropout_masks, synthetic_batches
 
 
-ATTACKS = ("sign_flip", "backdoor", "none", "alie", "ipm")
+ATTACKS = ("sign_flip", "backdoor", "none", "alie", "ipm", "min_max", "min_sum")
 
 
 @dataclass
@@ -48,7 +48,8 @@ class RoundConfig:
     defense: str = "krum"
     defense_cfg: Dict = field(default_factory=dict)
     # "sign_flip" (model_poisoning.py:274-276) | "backdoor" | "none" | "alie" | "ipm" (the colluding attacks of
-    # flr.attacks: one flr_collude_rows pass between the exchange and the defense)
+    # flr.attacks: one flr_collude_rows pass between the exchange and the defense) | "min_max" | "min_sum" (one
+    # flr_minmax_rows call in the same slot; whole rows: the all-gather exchange unless world == 1)
     attack: str = "sign_flip"
     num_attackers: int = 25              # f = int(0.2 K), clients 0..f-1 (experiment_matrix.py:67-68)
     seed: int = 42                       # run_experiments.py:43
@@ -62,7 +63,9 @@ class RoundConfig:
     # the defense's next collective would hang the round instead of failing it;
     # False keeps device errors loud at world 1 too
     fallback_device_errors: bool = True
-    attack_cfg: Dict = field(default_factory=dict)  # "z" (alie; default alie_z(K, f)), "epsilon" (ipm; default 0.5)
+    # "z" (alie; default alie_z(K, f)), "epsilon" (ipm; default 0.5), "perturb" (min_max / min_sum: "std" (default) |
+    # "sign" | "unit", the direction of flr.attacks.min_max_)
+    attack_cfg: Dict = field(default_factory=dict)
 
 
 def initial_global(spec: ModelSpec, seed: int, device) -> torch.Tensor:
@@ -88,6 +91,22 @@ class RoundEngine:
                 self._collude = (ops.COLLUDE_ALIE, float(alie_z(K, f) if z is None else z))
             else:
                 self._collude = (ops.COLLUDE_IPM, float(rcfg.attack_cfg.get("epsilon", 0.5)))
+        # Min-Max / Min-Sum: (objective, perturbation) of the one flr_minmax_rows call per round;
+        # attack_gamma: the last round's strength, a float64 device scalar (experiment logs)
+        self._minmax = None
+        self.attack_gamma: Optional[torch.Tensor] = None
+        if rcfg.attack in ("min_max", "min_sum"):
+            K, f = rcfg.num_clients, rcfg.num_attackers
+            if not 1 <= f < K:
+                raise ValueError(f"attack {rcfg.attack!r} needs 1 <= num_attackers < num_clients (got {f}, {K})")
+            perturb = rcfg.attack_cfg.get("perturb", "std")
+            if perturb not in PERTURBATIONS:
+                raise ValueError(f"attack_cfg['perturb'] = {perturb!r}: one of {', '.join(PERTURBATIONS)}")
+            if rcfg.exchange == "alltoall" and world > 1:  # "auto" takes the all-gather exchange below
+                raise ValueError(f"attack {rcfg.attack!r} needs whole client rows (row distances, not a "
+                                 "coordinate-wise statistic): use exchange='allgather' (a rank's all-to-all slice "
+                                 "is the whole matrix only at world 1)")
+            self._minmax = (ops.MINMAX_MAX if rcfg.attack == "min_max" else ops.MINMAX_SUM, PERTURBATIONS[perturb])
         defer = os.environ.get("FLR_DEFER_DEAD", "2")
         if defer == "1":  # loud: an old A/B script must not report numbers for another mode
             raise ValueError("FLR_DEFER_DEAD=1 (the dead-tap fill on a side stream beside the Krum chains) was "
@@ -116,7 +135,8 @@ class RoundEngine:
         self.defense = get_defense(rcfg.defense, cfg)
         mode = rcfg.exchange
         if mode == "auto":
-            mode = "alltoall" if (self.defense.supports_sharded and PW_SLICES % world == 0) else "allgather"
+            mode = "alltoall" if (self.defense.supports_sharded and PW_SLICES % world == 0
+                                  and self._minmax is None) else "allgather"
         if mode not in ("alltoall", "allgather"):
             raise ValueError(f"unknown exchange mode {rcfg.exchange!r}")
         if mode == "alltoall" and not self.defense.supports_sharded:
@@ -141,8 +161,10 @@ class RoundEngine:
         # training-order rounds (BaseDefense.order_free): the client matrix is in
         # the trainer's coordinate order, written by the last optimizer step;
         # gtrain is the global model in that order (FLR_ORDER=torch: off)
+        # Min-Max / Min-Sum read the round's global model beside the matrix: torch
+        # order, where global_flat lines up with the columns
         self.train_order = (getattr(self.defense, "order_free", False) and not self._wants_global
-                            and os.environ.get("FLR_ORDER", "train") != "torch")
+                            and self._minmax is None and os.environ.get("FLR_ORDER", "train") != "torch")
         bounds = None
         if self.train_order and getattr(self.defense, "needs_tap_blocks", False):
             # the reference-exact distances read the training-order matrix,
@@ -173,7 +195,8 @@ class RoundEngine:
         # other reader of X (the full / slice / client_matrix properties call
         # it); =0: written last in the training phase.  Not armed under the
         # colluding attacks (alie, ipm): their pass reads the benign rows and
-        # writes the attackers' rows whole, before the defense
+        # writes the attackers' rows whole, before the defense (min_max, min_sum
+        # likewise: they run in torch order, where nothing is deferred)
         self._dead: Optional[DeadTaps] = None
         self._x_stale = False  # set where run_round arms the deferral, cleared by materialize() alone
         if (self.train_order and world == 1 and self._collude is None and self.defense.__dict__.get("tap_blocks")
@@ -365,12 +388,14 @@ class RoundEngine:
         return self._publish(agg)
 
     def _apply_collusion(self, X: torch.Tensor) -> None:
-        """attack "alie" / "ipm": the attackers (clients 0..f-1, who trained
-        honestly) replace their rows of the exchanged matrix by the colluding
-        vector, computed from the benign rows — after the exchange, before the
-        defense, outside the captured training graph."""
+        """attack "alie" / "ipm" / "min_max" / "min_sum": the attackers (clients
+        0..f-1, who trained honestly) replace their rows of the exchanged matrix
+        by the colluding vector, computed from the benign rows — after the
+        exchange, before the defense, outside the captured training graph."""
         if self._collude is not None:
             ops.collude_rows(X, self.rcfg.num_attackers, *self._collude)
+        if self._minmax is not None:  # global_flat: still the model this round trained from
+            self.attack_gamma = ops.minmax_rows(X, self.rcfg.num_attackers, *self._minmax, self.global_flat)
 
     def _fallback(self, err: Exception, X: torch.Tensor) -> torch.Tensor:
         """robust_server.py:120-122: a failing defense falls back to FedAvg
