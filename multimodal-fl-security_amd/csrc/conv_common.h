@@ -123,7 +123,7 @@ inline bool geom_ok(int64_t K, int64_t B, int64_t Cin, int64_t H, int64_t W, int
 }  // namespace conv
 
 // Explicit-im2col path for convs with a short reduction (the 7x7 stem:
-// Cin*KH*KW = 147), implemented in train_conv_t.hip and used by the
+// Cin*KH*KW = 147), implemented in train_conv_t_im2col.hip and used by the
 // generic-layout entry points of train_conv.hip.
 namespace convt {
 bool im2col_eligible(const conv::Geom& g);

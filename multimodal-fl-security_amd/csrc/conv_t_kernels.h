@@ -1,0 +1,1142 @@
+// The tiled GEMM kernels behind every tap-major convolution, the im2col / stem
+// GEMMs and the batched GEMM: the shared epilogue, tgemm_kernel (fp32 LDS
+// images: exact f32 and the pipelined bf16x6 loop), sgemm_kernel (split at
+// stash), wsgemm_kernel (transposed images: the weight gradient),
+// treduce_kernel (split-K), then the tile / split-K policy and launch().
+#pragma once
+
+#include "conv_t_plans.h"
+
+namespace flr {
+namespace convt {
+
+// XCD-aware tile order.  The hardware deals workgroups round-robin over the 8
+// XCDs (linear id i -> XCD i % 8), each with its own 4 MB L2.  The remap gives
+// XCD x one contiguous range of logical tiles (bijective for any grid size), so
+// the tiles of one client — which re-read the same activations once per kernel
+// tap and the same weight slabs once per pixel tile — run on one XCD and share
+// its L2 instead of streaming every client through all eight.
+__device__ __forceinline__ void xcd_tile(int& bx, int& by, int& bz) {
+  const int gx = (int)gridDim.x, gy = (int)gridDim.y;
+  const int n = gx * gy * (int)gridDim.z;
+  const int lid = (int)blockIdx.x + gx * ((int)blockIdx.y + gy * (int)blockIdx.z);
+  const int xcd = lid & 7, slot = lid >> 3;
+  const int q = n >> 3, r = n & 7;
+  const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
+  bx = t % gx;
+  by = (t / gx) % gy;
+  bz = t / (gx * gy);
+}
+
+template <class P> struct has_sq : std::false_type {};
+template <bool V> struct has_sq<WgtT<V>> : std::true_type {};
+
+// Sum over the workgroup in a fixed order (fp64): each thread's own value, a
+// butterfly over the wave, the waves in index order; the result is thread 0's.
+// Every thread of the workgroup must call it (one barrier).
+__device__ __forceinline__ double block_sumsq(double s, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  double t = 0.0;
+  if (threadIdx.x == 0)
+    for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
+  return t;
+}
+
+// the epilogue's optional addend (DgradT: the other gradient path of a residual
+// block, summed where autograd would add the two paths)
+template <class P> __device__ inline const float* plan_add(const P&) { return nullptr; }
+__device__ inline const float* plan_add(const DgradT& p) { return p.add; }
+
+// ---- the epilogue ---------------------------------------------------------------
+// Every GEMM kernel's: this wave's MSW x NS accumulator blocks (32 x 32 each) to
+// the plan's output (S == 1: epilogue operands loaded before the stores) or to
+// the split-K partials.  Block (i, j) lies in the tile at (m0 + off.m[i],
+// n0 + off.n[j]), at (off.wr, off.wc) inside it; C/D map of the 32x32 MFMA:
+// col = lane & 31 (l32), row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5) (h).
+template <int MSW, int NS>
+struct TileOffs {
+  int m[MSW], n[NS];  // the blocks' tiles: row / column offsets from (m0, n0)
+  int wr, wc;         // the wave's block inside each tile (0: the tile is the block)
+};
+template <class Plan, int MSW, int NS>
+__device__ __forceinline__ void store_tiles(const Plan& pl, int S, float* __restrict__ part, int k, int split, int m0,
+                                            int n0, int h, int l32, int M, int N, f32x16 (&acc)[MSW][NS],
+                                            const TileOffs<MSW, NS> off) {
+#pragma unroll
+  for (int i = 0; i < MSW; ++i)
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      const int tm0 = m0 + off.m[i], tn0 = n0 + off.n[j];
+      if (S == 1 && pl.linear()) {
+        float* base = pl.out() + pl.tile_base(k, tm0, tn0);
+        const int64_t ldm = pl.ldm();
+        const int nl = off.wc + l32;
+        if constexpr (std::is_base_of<BGemmArgs, Plan>::value) {
+          if (pl.bias) {  // the batched GEMM's bias: one value per lane column, bias + v
+            const float bv = tn0 + nl < N ? pl.bias[k * pl.bias_k + tn0 + nl] : 0.f;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[i][j][e] = bv + acc[i][j][e];
+          }
+        }
+        if (const float* abase = plan_add(pl)) {  // all 16 addends in flight before the first store
+          abase += pl.tile_base(k, tm0, tn0);
+          float av[16];
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int ml = off.wr + (e & 3) + 8 * (e >> 2) + 4 * h;
+            av[e] = (tm0 + ml < M && tn0 + nl < N) ? abase[ml * ldm + nl] : 0.f;
+          }
+#pragma unroll
+          for (int e = 0; e < 16; ++e) acc[i][j][e] = __fadd_rn(acc[i][j][e], av[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 16; ++e) {
+          const int ml = off.wr + (e & 3) + 8 * (e >> 2) + 4 * h;
+          if (tm0 + ml < M && tn0 + nl < N) base[ml * ldm + nl] = acc[i][j][e];
+        }
+        continue;
+      }
+      if constexpr (std::is_same<Plan, DgradT>::value) {
+        if (S == 1 && pl.add) {  // parity-class stores: the addends loaded before any store
+          int64_t ix[16];
+          float av[16];
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int m = tm0 + off.wr + (e & 3) + 8 * (e >> 2) + 4 * h;
+            const int n = tn0 + off.wc + l32;
+            ix[e] = (m < M && n < N) ? pl.index(k, m, n) : -1;
+            av[e] = ix[e] >= 0 ? pl.add[ix[e]] : 0.f;
+          }
+#pragma unroll
+          for (int e = 0; e < 16; ++e)
+            if (ix[e] >= 0) pl.dx[ix[e]] = __fadd_rn(acc[i][j][e], av[e]);
+          continue;
+        }
+      }
+      if constexpr (std::is_base_of<BGemmArgs, Plan>::value) {
+        if (S == 1) {
+          pl.store_tile(k, tm0, tn0, off.wr + 4 * h, off.wc + l32, acc[i][j], M, N);
+          continue;
+        }
+      }
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int m = tm0 + off.wr + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int n = tn0 + off.wc + l32;
+        if (m < M && n < N) {
+          if (S == 1) pl.store(k, m, n, acc[i][j][e]);
+          else part[(((int64_t)split * pl.g.Kc + k) * M + m) * N + n] = acc[i][j][e];
+        }
+      }
+    }
+}
+
+// wave (wm, wn)'s blocks in the 64 x 64 sub-tiles of a (64*MS) x (64*NS) workgroup tile
+template <int MS, int NS>
+__device__ __forceinline__ TileOffs<MS, NS> sub_tiles(int wm, int wn) {
+  TileOffs<MS, NS> off;
+#pragma unroll
+  for (int i = 0; i < MS; ++i) off.m[i] = BM * i;
+#pragma unroll
+  for (int j = 0; j < NS; ++j) off.n[j] = BN * j;
+  off.wr = 32 * wm;
+  off.wc = 32 * wn;
+  return off;
+}
+
+// The workgroup tile's clip-norm partial (WgtT with sq, S == 1; under split-K the
+// treduce pass writes them): fp64, each thread's values in (i, j, e) order, then
+// block_sumsq (red: the kernel's THREADS / 64 doubles of LDS); slot = the tile's
+// index in the grid.  Every thread must call it.
+template <class Plan, int MSW, int NS>
+__device__ __forceinline__ void store_sumsq(const Plan& pl, int k, int bx, int by, int m0, int n0, int h, int l32, int M,
+                                            int N, const f32x16 (&acc)[MSW][NS], const TileOffs<MSW, NS> off,
+                                            double* red) {
+  double sq = 0.0;
+#pragma unroll
+  for (int i = 0; i < MSW; ++i)
+#pragma unroll
+    for (int j = 0; j < NS; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int m = m0 + off.m[i] + off.wr + (e & 3) + 8 * (e >> 2) + 4 * h;
+        const int n = n0 + off.n[j] + off.wc + l32;
+        const double v = (m < M && n < N) ? (double)acc[i][j][e] : 0.0;
+        sq += v * v;
+      }
+  const double t = block_sumsq(sq, red);
+  if (threadIdx.x == 0) pl.sq[(int64_t)k * pl.sq_ld + by * (int)gridDim.x + bx] = t;
+}
+
+// ---- the kernel ---------------------------------------------------------------
+// Workgroup tile (64*MS) x (64*NS): MS A sub-tiles and NS B sub-tiles of 64
+// rows each are staged per K-tile; wave (wm, wn) owns rows 32 wm .. +31 and
+// columns 32 wn .. +31 of every (i, j) sub-tile pair, so a fragment read from
+// LDS feeds NS (A) or MS (B) MFMAs and the MS*NS accumulator chains are
+// independent.  MS or NS = 2 halves the loads, LDS traffic and barriers per
+// MFMA of the 64 x 64 tile.
+template <class Plan, int MS, int NS, int X6>
+__global__ __launch_bounds__(THREADS, 2) void tgemm_kernel(const Plan pl, int S, float* __restrict__ part, int remap,
+                                                           int prio) {
+  __shared__ __attribute__((aligned(16))) float As[2][MS][TILE];
+  __shared__ __attribute__((aligned(16))) float Bs[2][NS][TILE];
+  int bx = (int)blockIdx.x, by = (int)blockIdx.y, bz = (int)blockIdx.z;
+  if (remap & 1) xcd_tile(bx, by, bz);
+  const int k = bz / S, split = bz % S;
+  const int M = pl.M(), N = pl.N(), R = pl.R();
+  const int ktiles = cdiv(R, BK);
+  const int rbeg = (int)((int64_t)ktiles * split / S) * BK;
+  const int rend = std::min(R, (int)((int64_t)ktiles * (split + 1) / S) * BK);
+  const int m0 = by * BM * MS, n0 = bx * BN * NS;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int h = lane >> 5, l32 = lane & 31;
+
+  typename Plan::State sa[MS], sb[NS];
+#pragma unroll
+  for (int i = 0; i < MS; ++i) sa[i] = pl.init(k, m0 + BM * i, n0, tid);
+#pragma unroll
+  for (int j = 0; j < NS; ++j) sb[j] = pl.init(k, m0, n0 + BN * j, tid);
+  float ra[MS][8], rb[NS][8];
+  f32x16 acc[MS][NS];
+#pragma unroll
+  for (int i = 0; i < MS; ++i)
+#pragma unroll
+    for (int j = 0; j < NS; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  auto load = [&](int r) {
+#pragma unroll
+    for (int i = 0; i < MS; ++i) pl.load_a(sa[i], r, ra[i]);
+#pragma unroll
+    for (int j = 0; j < NS; ++j) pl.load_b(sb[j], r, rb[j]);
+  };
+  auto stash_all = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < MS; ++i) stash<Plan::LA>(As[buf][i], ra[i], tid);
+#pragma unroll
+    for (int j = 0; j < NS; ++j) stash<Plan::LB>(Bs[buf][j], rb[j], tid);
+  };
+  if constexpr (X6 == 2) {
+    // Software-pipelined bf16x6 loop (the default form).  A wave issues in
+    // order, so its fragment reads, bf16 splits, LDS stash and global loads
+    // only overlap its own MFMAs when they sit between them in one basic
+    // block.  Per K-tile t (two 16-deep k-steps, fragments F of step 0 ready):
+    //   phase 0: MFMAs of step 0 || read + split step 1 -> F1, stash tile t+1
+    //   barrier (publishes tile t+1; every read of the buffer it reuses is done)
+    //   phase 1: MFMAs of step 1 || global loads of tile t+2, read + split
+    //            step 0 of tile t+1 -> F0
+    // Tiles past the last are clamped to it (duplicate loads / stashes / splits
+    // that nothing consumes), so both phases are branch-free.
+    static_assert(BK == 32, "two k-steps per K-tile");
+    const int ntile = rend > rbeg ? (rend - rbeg + BK - 1) / BK : 0;
+    if (ntile > 0) {
+      const int rlast = rbeg + (ntile - 1) * BK;
+      bf16x8 ah0[MS], am0[MS], al0[MS], bh0[NS], bm0[NS], bl0[NS];
+      bf16x8 ah1[MS], am1[MS], al1[MS], bh1[NS], bm1[NS], bl1[NS];
+      float va[MS][8], vb[NS][8];
+      auto read_frags = [&](int buf, int s) {
+#pragma unroll
+        for (int i = 0; i < MS; ++i) frag8<Plan::LA>(As[buf][i], 32 * wm + l32, 16 * s + 8 * h, va[i]);
+#pragma unroll
+        for (int j = 0; j < NS; ++j) frag8<Plan::LB>(Bs[buf][j], 32 * wn + l32, 16 * s + 8 * h, vb[j]);
+      };
+#define FLR_SPLIT_ALL(AH, AM, AL, BH, BM, BL)                                       \
+  _Pragma("unroll") for (int i = 0; i < MS; ++i) split3(va[i], AH[i], AM[i], AL[i]); \
+  _Pragma("unroll") for (int j = 0; j < NS; ++j) split3(vb[j], BH[j], BM[j], BL[j]);
+#define FLR_X6P(AV, BV)                                                                           \
+  _Pragma("unroll") for (int i = 0; i < MS; ++i) _Pragma("unroll") for (int j = 0; j < NS; ++j) \
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AV[i], BV[j], acc[i][j], 0, 0, 0);
+#define FLR_X6P_ALL(AH, AM, AL, BH, BM, BL) \
+  FLR_X6P(AM, BM) FLR_X6P(AH, BL) FLR_X6P(AL, BH) FLR_X6P(AH, BM) FLR_X6P(AM, BH) FLR_X6P(AH, BH)
+      load(rbeg);
+      stash_all(0);
+      __syncthreads();
+      load(std::min(rbeg + BK, rlast));
+      read_frags(0, 0);
+      FLR_SPLIT_ALL(ah0, am0, al0, bh0, bm0, bl0)
+      int cur = 0;
+      for (int t = 0; t < ntile; ++t) {
+        const int r0 = rbeg + t * BK;
+        // phase 0
+        read_frags(cur, 1);
+        FLR_X6P_ALL(ah0, am0, al0, bh0, bm0, bl0)
+        FLR_SPLIT_ALL(ah1, am1, al1, bh1, bm1, bl1)
+        stash_all(cur ^ 1);
+        __syncthreads();
+        // phase 1
+        load(std::min(r0 + 2 * BK, rlast));
+        read_frags(cur ^ 1, 0);
+        FLR_X6P_ALL(ah1, am1, al1, bh1, bm1, bl1)
+        FLR_SPLIT_ALL(ah0, am0, al0, bh0, bm0, bl0)
+        cur ^= 1;
+      }
+#undef FLR_SPLIT_ALL
+#undef FLR_X6P
+#undef FLR_X6P_ALL
+    }
+  } else {
+  if (rbeg < rend) {
+    load(rbeg);
+    stash_all(0);
+  }
+  __syncthreads();
+  int cur = 0;
+  for (int r0 = rbeg; r0 < rend; r0 += BK) {
+    const bool more = r0 + BK < rend;
+    if (more) load(r0 + BK);  // in flight during the MFMAs below
+    if constexpr (X6 != 0) {
+#pragma unroll
+      for (int s = 0; s < BK / 16; ++s) {
+        bf16x8 ah[MS], am[MS], al[MS], bh[NS], bm[NS], bl[NS];
+#pragma unroll
+        for (int i = 0; i < MS; ++i) {
+          float v[8];
+          frag8<Plan::LA>(As[cur][i], 32 * wm + l32, 16 * s + 8 * h, v);
+          if constexpr (X6 == 3) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) ah[i][q] = am[i][q] = al[i][q] = (__bf16)v[q];
+          } else {
+            split3(v, ah[i], am[i], al[i]);
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < NS; ++j) {
+          float v[8];
+          frag8<Plan::LB>(Bs[cur][j], 32 * wn + l32, 16 * s + 8 * h, v);
+          if constexpr (X6 == 3) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) bh[j][q] = bm[j][q] = bl[j][q] = (__bf16)v[q];
+          } else {
+            split3(v, bh[j], bm[j], bl[j]);
+          }
+        }
+        if (prio) __builtin_amdgcn_s_setprio(1);
+        if constexpr (X6 >= 3) {
+          // product-major: the MS*NS accumulator chains interleave, so a chain's
+          // next MFMA never waits on its own previous one (small terms first)
+#define FLR_X6_STEP(AV, BV)                                                              \
+  _Pragma("unroll") for (int i = 0; i < MS; ++i) _Pragma("unroll") for (int j = 0; j < NS; ++j) \
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AV[i], BV[j], acc[i][j], 0, 0, 0);
+          FLR_X6_STEP(am, bm)
+          FLR_X6_STEP(ah, bl)
+          FLR_X6_STEP(al, bh)
+          FLR_X6_STEP(ah, bm)
+          FLR_X6_STEP(am, bh)
+          FLR_X6_STEP(ah, bh)
+#undef FLR_X6_STEP
+        } else {
+#pragma unroll
+          for (int i = 0; i < MS; ++i)
+#pragma unroll
+            for (int j = 0; j < NS; ++j) {  // small terms first
+              f32x16 c = acc[i][j];
+              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bm[j], c, 0, 0, 0);
+              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], c, 0, 0, 0);
+              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], c, 0, 0, 0);
+              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bm[j], c, 0, 0, 0);
+              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bh[j], c, 0, 0, 0);
+              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], c, 0, 0, 0);
+              acc[i][j] = c;
+            }
+        }
+        if (prio) __builtin_amdgcn_s_setprio(0);
+      }
+    } else {
+      f32x4 fa[MS][4], fb[NS][4];  // all of the tile's fragments first: the reads overlap the MFMA chain
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj) {
+#pragma unroll
+        for (int i = 0; i < MS; ++i) fa[i][jj] = frag<Plan::LA>(As[cur][i], 32 * wm + l32, jj, h);
+#pragma unroll
+        for (int j = 0; j < NS; ++j) fb[j][jj] = frag<Plan::LB>(Bs[cur][j], 32 * wn + l32, jj, h);
+      }
+      __builtin_amdgcn_sched_barrier(0);  // keep the reads ahead of the chain (the scheduler would interleave them)
+#pragma unroll
+      for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+          for (int i = 0; i < MS; ++i)
+#pragma unroll
+            for (int j = 0; j < NS; ++j)
+              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i][jj][t], fb[j][jj][t], acc[i][j], 0, 0, 0);
+    }
+    if (more) stash_all(cur ^ 1);
+    __syncthreads();
+    cur ^= 1;
+  }
+  }  // old loop (FLR_GEMM=f32 | chain | old | A)
+  const TileOffs<MS, NS> off = sub_tiles<MS, NS>(wm, wn);
+  store_tiles<Plan, MS, NS>(pl, S, part, k, split, m0, n0, h, l32, M, N, acc, off);
+  if constexpr (has_sq<Plan>::value) {
+    if (S == 1 && pl.sq) {
+      __shared__ double red[THREADS / 64];
+      store_sumsq(pl, k, bx, by, m0, n0, h, l32, M, N, acc, off, red);
+    }
+  }
+}
+
+// ---- the split-at-stash form (FLR_GEMM=stash) ------------------------------
+// Each value is split into bf16 hi/mid/lo ONCE, by the thread that loaded it,
+// instead of once per wave that reads its fragment: the LDS holds three bf16
+// images per sub-tile, [64 rows][32 k] with the four 16-B k-chunks of a row
+// XOR-swizzled by zswz(row) (no padding: conflict-free ds_read_b128 fragment
+// reads and ds_write_b128 stashes under both stash mappings, checked
+// exhaustively over the lane groups), and an MFMA fragment is one
+// ds_read_b128 per term.  48 KB per 128 x 128 tile, so three workgroups fit a
+// CU's LDS (the padded 80-B rows took 61 KB: two).  The loads are k-contiguous (thread: row tid & 63,
+// k 8 (tid >> 6) .. +7, the plans' init8 / load_a8 / load_b8), so a thread's
+// stash is three 16-B writes per sub-tile.  Single LDS buffer, two barriers
+// per K-tile; the split of tile t+1 sits between tile t's MFMAs.  Every
+// accumulator sees the same bf16 products in the same order as the other
+// bf16x6 forms: the results are bit-identical to them.
+constexpr int SB = 32;            // bf16 per image row (chunks swizzled, no pad)
+constexpr int TERM_B = 64 * SB;   // bf16 per term image
+// bf16 offset of (row, k-chunk c = k / 8) in a row-major term image
+__device__ __forceinline__ int zimg(int row, int c) {
+  const int f = ((row >> 2) & 1) | ((((row >> 1) ^ (row >> 3)) & 1) << 1);
+  return row * SB + 8 * (c ^ f);
+}
+// waves per SIMD the split-at-stash kernels are compiled for (3 would mean at
+// most 168 VGPRs, three 128 x 128 workgroups per CU)
+constexpr int SG_OCC = 2;
+template <class P> struct has_k8 : std::false_type {};
+template <> struct has_k8<FwdT> : std::true_type {};
+template <> struct has_k8<DgradT> : std::true_type {};
+// WgtT has k8 loads but stays on the pipelined form: its x operand is k-contiguous
+// only along pixels, so the k8 mapping puts the lanes on channels (sxc apart, a
+// cache line per lane): l1 wgrad 202 -> 366 us measured.
+template <int A, int B> struct has_k8<BGemm<A, B>> : std::true_type {};
+// Two LDS stages (one barrier per K-tile, tile t+1 stashed into the other stage
+// during tile t's MFMAs, one workgroup per CU by LDS) were measured 20-35 %
+// slower than this one-stage form at two workgroups per CU (C3 conv and C4
+// GEMM shapes, profiles/r3_sgemm_db.txt).
+//
+// Producer / consumer waves (8 consumer waves over a 128 x 256 tile + 4 waves that
+// only stash into the other of two LDS stages, one barrier per K-tile; or 4 + 4 over
+// 128 x 128) were measured, bit-identical, 7-40 % slower than this loop on the C4
+// GEMM and C3 conv shapes (profiles/r3_gemm_loop/pc8_*): the consumer waves, which
+// wait for their fragment reads after every barrier, set the pace.
+//
+// A half-phase schedule (one barrier per 16-deep k-step; waves 0-1 stash k-step 0's
+// half of the next tile beside k-step 1's MFMAs, waves 2-3 k-step 1's half beside
+// the next k-step 0; lane pairs instead of quads on k-contiguous rows) was
+// bit-identical and 0-25 % slower per conv layer, 8-27 % on the C4 GEMMs, C3 round
+// 60.0 -> 61.5 ms (profiles/r3_gemm_loop/half_phase.txt): twice the barriers per MFMA.
+// Issuing tile t+2's global loads before the first barrier instead of after the
+// stash: neutral on the GEMMs, C3 round 58.7 -> 59.6 ms (same file).
+// NAR (narrow N, the l4 convolutions' N = B * 1 * 1 = 32 pixels): NS = 1 and the four
+// waves stacked along M over MS 64-row A sub-tiles, each wave MS / 2 MFMA blocks of
+// 32 x 32 on the first 32 columns of the B image — a 64-wide N tile would leave half
+// its MFMAs on empty columns.  Same products per output: bit-identical.
+template <class Plan, int MS, int NS, int ABL = 0, bool NAR = false>
+__device__ __forceinline__ void sgemm_body(const Plan& pl, int S, float* __restrict__ part, int remap) {
+  static_assert(!NAR || (NS == 1 && (MS == 2 || MS == 4)), "narrow tiles: 128 or 256 x 32");
+  constexpr int MSW = NAR ? MS / 2 : MS;  // MFMA blocks per wave along M (NAR), or A sub-tiles
+  __shared__ __attribute__((aligned(16))) __bf16 Ls[MS + NS][3][TERM_B];
+  int bx = (int)blockIdx.x, by = (int)blockIdx.y, bz = (int)blockIdx.z;
+  if (remap & 1) xcd_tile(bx, by, bz);
+  if (remap >> 8) odd_slot_controls(remap);
+  const int k = bz / S, split = bz % S;
+  const int M = pl.M(), N = pl.N(), R = pl.R();
+  const int ktiles = cdiv(R, BK);
+  const int rbeg = (int)((int64_t)ktiles * split / S) * BK;
+  const int rend = std::min(R, (int)((int64_t)ktiles * (split + 1) / S) * BK);
+  const int m0 = by * BM * MS, n0 = bx * BN * NS;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int h = lane >> 5, l32 = lane & 31;
+  // this thread's stash row and k offset per operand (Plan::QUAD_A / QUAD_B)
+  const int srowA = stash_row<Plan::QUAD_A>(tid), skA = stash_k<Plan::QUAD_A>(tid);
+  const int srowB = stash_row<Plan::QUAD_B>(tid), skB = stash_k<Plan::QUAD_B>(tid);
+
+  typename Plan::State8 sa[MS], sb[NS];
+#pragma unroll
+  for (int i = 0; i < MS; ++i) sa[i] = pl.init8(k, m0 + BM * i, n0, tid);
+#pragma unroll
+  for (int j = 0; j < NS; ++j) sb[j] = pl.init8(k, m0, n0 + BN * j, tid);
+  // one register set: a second one, keeping two tiles of global loads in flight, was measured: no gain
+  // at the C3 conv and C4 GEMM shapes — the loop is not load-latency-bound
+  float ra[MS][8], rb[NS][8];
+  bf16x8 pa[MS][3], pb[NS][3];
+  f32x16 acc[MSW][NS];
+#pragma unroll
+  for (int i = 0; i < MSW; ++i)
+#pragma unroll
+    for (int j = 0; j < NS; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  // this wave's MFMA block i: A sub-tile and row band (NAR: wave-stacked), and its
+  // row / column offset from (m0, n0)
+  auto a_sub = [&](int i) { return NAR ? (wave * MSW + i) >> 1 : i; };
+  auto a_row = [&](int i) { return NAR ? 32 * ((wave * MSW + i) & 1) + l32 : 32 * wm + l32; };
+  auto b_row = [&]() { return NAR ? l32 : 32 * wn + l32; };
+  auto m_off = [&](int i) { return NAR ? 32 * (wave * MSW + i) : BM * i + 32 * wm; };
+  auto n_off = [&](int j) { return NAR ? 0 : BN * j + 32 * wn; };
+  auto load = [&](int r) {
+#pragma unroll
+    for (int i = 0; i < MS; ++i) pl.load_a8(sa[i], r, ra[i]);
+#pragma unroll
+    for (int j = 0; j < NS; ++j) pl.load_b8(sb[j], r, rb[j]);
+  };
+  auto split_all = [&]() {
+#pragma unroll
+    for (int i = 0; i < MS; ++i) split3(ra[i], pa[i][0], pa[i][1], pa[i][2]);
+#pragma unroll
+    for (int j = 0; j < NS; ++j) split3(rb[j], pb[j][0], pb[j][1], pb[j][2]);
+  };
+  auto write_all = [&]() {
+#pragma unroll
+    for (int i = 0; i < MS; ++i)
+#pragma unroll
+      for (int t = 0; t < 3; ++t) *reinterpret_cast<bf16x8*>(&Ls[i][t][zimg(srowA, skA >> 3)]) = pa[i][t];
+#pragma unroll
+    for (int j = 0; j < NS; ++j)
+#pragma unroll
+      for (int t = 0; t < 3; ++t) *reinterpret_cast<bf16x8*>(&Ls[MS + j][t][zimg(srowB, skB >> 3)]) = pb[j][t];
+  };
+  // Both k-steps' fragments are read before the first MFMA, so the second
+  // k-step's LDS latency runs under the first's MFMAs and the reads are complete
+  // by the barrier that follows (the compiler keeps the reads ahead of that
+  // barrier and moves the second k-step's MFMAs after it).  Reading per k-step
+  // (same operands, same MFMA order) was the A/B: profiles/r6_conv/README.md.
+  auto compute_tile = [&]() {
+    constexpr int NKS = BK / 16;
+    bf16x8 fa[NKS][MSW][3], fb[NKS][NS][3];
+#pragma unroll
+    for (int s = 0; s < NKS; ++s) {
+      const int ko = 16 * s + 8 * h;
+#pragma unroll
+      for (int i = 0; i < MSW; ++i)
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+          fa[s][i][q] = *reinterpret_cast<const bf16x8*>(&Ls[a_sub(i)][q][zimg(a_row(i), ko >> 3)]);
+#pragma unroll
+      for (int j = 0; j < NS; ++j)
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+          fb[s][j][q] = *reinterpret_cast<const bf16x8*>(&Ls[MS + j][q][zimg(b_row(), ko >> 3)]);
+    }
+    __builtin_amdgcn_sched_barrier(0);  // the scheduler would sink the second k-step's reads again
+#define FLR_SX(TA, TB)                                                                              \
+  _Pragma("unroll") for (int i = 0; i < MSW; ++i) _Pragma("unroll") for (int j = 0; j < NS; ++j) \
+    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][i][TA], fb[s][j][TB], acc[i][j], 0, 0, 0);
+#pragma unroll
+    for (int s = 0; s < NKS; ++s) {
+      // product-major, small terms first (term 0 = hi, 1 = mid, 2 = lo)
+      FLR_SX(1, 1) FLR_SX(0, 2) FLR_SX(2, 0) FLR_SX(0, 1) FLR_SX(1, 0) FLR_SX(0, 0)
+    }
+#undef FLR_SX
+  };
+  const int ntile = rend > rbeg ? (rend - rbeg + BK - 1) / BK : 0;
+  if (ntile > 0) {
+    const int rlast = rbeg + (ntile - 1) * BK;
+    load(rbeg);
+    split_all();
+    write_all();
+    load(std::min(rbeg + BK, rlast));
+    __syncthreads();
+    // one K-tile: the MFMAs of tile t from the LDS images, the split of tile t+1
+    // between them, its stash, then the global loads of tile t+2 into the
+    // registers just freed (clamped past the last tile: duplicates)
+    auto tile_body = [&](int t) {
+      const int r0 = rbeg + t * BK;
+      // ABL (tools build only, timing ablations with wrong results): 1 no global loads,
+      // 2 no stash writes, 4 no first barrier, 8 no split, 16 no MFMAs / fragment reads
+      // (profiles/r3_gemm_loop/: without the stash writes the loop is 36 % shorter; with
+      // only the fragment reads and MFMAs it runs at ~0.55 of the bf16x6 ceiling)
+      if constexpr (!(ABL & 16)) compute_tile();
+      if constexpr (!(ABL & 8)) split_all();
+      if constexpr (!(ABL & 4)) __syncthreads();  // every wave's fragment reads of tile t are done
+      if constexpr (!(ABL & 2)) write_all();
+      if constexpr (!(ABL & 1)) load(std::min(r0 + 2 * BK, rlast));
+      __syncthreads();
+    };
+    for (int t = 0; t < ntile; ++t) tile_body(t);
+  }
+  TileOffs<MSW, NS> off;
+#pragma unroll
+  for (int i = 0; i < MSW; ++i) off.m[i] = m_off(i);
+#pragma unroll
+  for (int j = 0; j < NS; ++j) off.n[j] = n_off(j);
+  off.wr = off.wc = 0;
+  store_tiles<Plan, MSW, NS>(pl, S, part, k, split, m0, n0, h, l32, M, N, acc, off);
+}
+
+template <class Plan, int MS, int NS, int ABL = 0, bool NAR = false>
+__global__ __launch_bounds__(THREADS, SG_OCC) void sgemm_kernel(const Plan pl, int S, float* __restrict__ part,
+                                                                 int remap) {
+  sgemm_body<Plan, MS, NS, ABL, NAR>(pl, S, part, remap);
+}
+
+// ---- the weight gradient on split-at-stash images, transposed ----------------
+// Both operands of dW are contiguous along the reduction (pixels), so the loads
+// put a half-wave on 32 consecutive pixels of one channel (coalesced) and each
+// thread holds 8 consecutive channels at one pixel (StateT).  The split images
+// are [k = 32][row = 64] bf16 per term (128-B k-rows, 16-B chunks of 8 rows
+// XOR-swizzled by tswz(k): conflict-free ds_write_b128 stashes and transposed
+// reads), and an MFMA fragment (8 consecutive k of one row) is two
+// ds_read_b64_tr_b16: each 16-lane group reads a 4 k x 16 row block and gets it
+// column-major.  Products and their order per accumulator are the other bf16x6
+// forms': bit-identical dw and clip-norm partials.
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+__host__ __device__ constexpr int tswz(int k) { return (k & 3) | ((((k >> 1) ^ (k >> 2)) & 1) << 2); }
+constexpr int TIMG = 32 * 64;  // bf16 per transposed term image
+
+template <class Plan, int MS, int NS, bool TA, bool TB>
+__global__ __launch_bounds__(THREADS, SG_OCC) void wsgemm_kernel(const Plan pl, int S, float* __restrict__ part,
+                                                                  int remap) {
+  // a term image: transposed [32 k][64 rows] (TIMG) or row-major [64 rows][SB] (TERM_B)
+  constexpr int IMG = (TA || TB) && !(TA && TB) ? TERM_B : (TA ? TIMG : TERM_B);
+  __shared__ __attribute__((aligned(16))) __bf16 Lt[MS + NS][3][IMG];
+  int bx = (int)blockIdx.x, by = (int)blockIdx.y, bz = (int)blockIdx.z;
+  if (remap & 1) xcd_tile(bx, by, bz);
+  if (remap >> 8) odd_slot_controls(remap);
+  const int k = bz / S, split = bz % S;
+  const int M = pl.M(), N = pl.N(), R = pl.R();
+  const int ktiles = cdiv(R, BK);
+  const int rbeg = (int)((int64_t)ktiles * split / S) * BK;
+  const int rend = std::min(R, (int)((int64_t)ktiles * (split + 1) / S) * BK);
+  const int m0 = by * BM * MS, n0 = bx * BN * NS;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int h = lane >> 5, l32 = lane & 31;
+  // stash slot: k = tid & 31, chunk (tid >> 5) ^ tswz(k)
+  const int skq = tid & 31;
+  const int sidx = skq * 64 + 8 * ((tid >> 5) ^ tswz(skq));
+  // transposed-read lane addresses (bf16 index in a term image) for the two 4-k halves
+  // of this lane's 8-k fragment; k-step s adds 16 * 64
+  const int gq = (lane & 15) >> 2, gp = lane & 3, g1 = (lane >> 4) & 1;
+  int ra_off[2], rb_off[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int kk = 8 * h + 4 * j + gq;
+    const int ca = 4 * wm + 2 * g1 + (gp >> 1), cb = 4 * wn + 2 * g1 + (gp >> 1);
+    ra_off[j] = kk * 64 + 8 * (ca ^ tswz(kk)) + 4 * (gp & 1);
+    rb_off[j] = kk * 64 + 8 * (cb ^ tswz(kk)) + 4 * (gp & 1);
+  }
+
+  // row-major images: the split-at-stash kernel's stash slot and fragment rows
+  const int srowA = stash_row<Plan::QUAD_A>(tid), skA = stash_k<Plan::QUAD_A>(tid);
+  const int srowB = stash_row<Plan::QUAD_B>(tid), skB = stash_k<Plan::QUAD_B>(tid);
+  using SA = std::conditional_t<TA, typename Plan::StateT, typename Plan::State8>;
+  using SBt = std::conditional_t<TB, typename Plan::StateT, typename Plan::State8>;
+  SA sa[MS];
+  SBt sb[NS];
+#pragma unroll
+  for (int i = 0; i < MS; ++i) {
+    if constexpr (TA) sa[i] = pl.initT(k, m0 + BM * i, n0, tid);
+    else sa[i] = pl.init8(k, m0 + BM * i, n0, tid);
+  }
+#pragma unroll
+  for (int j = 0; j < NS; ++j) {
+    if constexpr (TB) sb[j] = pl.initT(k, m0, n0 + BN * j, tid);
+    else sb[j] = pl.init8(k, m0, n0 + BN * j, tid);
+  }
+  // one register set: a second one, keeping two tiles of global loads in flight, was measured: no gain
+  // at the C3 conv and C4 GEMM shapes — the loop is not load-latency-bound
+  float ra[MS][8], rb[NS][8];
+  bf16x8 pa[MS][3], pb[NS][3];
+  f32x16 acc[MS][NS];
+#pragma unroll
+  for (int i = 0; i < MS; ++i)
+#pragma unroll
+    for (int j = 0; j < NS; ++j)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
+  auto load = [&](int r) {
+#pragma unroll
+    for (int i = 0; i < MS; ++i) {
+      if constexpr (TA) pl.load_at8(sa[i], r, ra[i]);
+      else pl.load_a8(sa[i], r, ra[i]);
+    }
+#pragma unroll
+    for (int j = 0; j < NS; ++j) {
+      if constexpr (TB) pl.load_bt8(sb[j], r, rb[j]);
+      else pl.load_b8(sb[j], r, rb[j]);
+    }
+  };
+  auto split_all = [&]() {
+#pragma unroll
+    for (int i = 0; i < MS; ++i) split3(ra[i], pa[i][0], pa[i][1], pa[i][2]);
+#pragma unroll
+    for (int j = 0; j < NS; ++j) split3(rb[j], pb[j][0], pb[j][1], pb[j][2]);
+  };
+  auto write_all = [&]() {
+#pragma unroll
+    for (int i = 0; i < MS; ++i)
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+        *reinterpret_cast<bf16x8*>(&Lt[i][t][TA ? sidx : zimg(srowA, skA >> 3)]) = pa[i][t];
+#pragma unroll
+    for (int j = 0; j < NS; ++j)
+#pragma unroll
+      for (int t = 0; t < 3; ++t)
+        *reinterpret_cast<bf16x8*>(&Lt[MS + j][t][TB ? sidx : zimg(srowB, skB >> 3)]) = pb[j][t];
+  };
+  auto tread = [&](const __bf16* img, const int (&off)[2], int s) -> bf16x8 {
+    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + off[0] + 1024 * s));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + off[1] + 1024 * s));
+    typedef short s16x8 __attribute__((ext_vector_type(8)));
+    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(bf16x8, v);
+  };
+  auto compute_tile = [&]() {
+#pragma unroll
+      for (int s = 0; s < BK / 16; ++s) {
+        bf16x8 fa[MS][3], fb[NS][3];
+#pragma unroll
+        for (int i = 0; i < MS; ++i)
+#pragma unroll
+          for (int q = 0; q < 3; ++q) {
+            if constexpr (TA) fa[i][q] = tread(Lt[i][q], ra_off, s);
+            else fa[i][q] = *reinterpret_cast<const bf16x8*>(&Lt[i][q][zimg(32 * wm + l32, 2 * s + h)]);
+          }
+#pragma unroll
+        for (int j = 0; j < NS; ++j)
+#pragma unroll
+          for (int q = 0; q < 3; ++q) {
+            if constexpr (TB) fb[j][q] = tread(Lt[MS + j][q], rb_off, s);
+            else fb[j][q] = *reinterpret_cast<const bf16x8*>(&Lt[MS + j][q][zimg(32 * wn + l32, 2 * s + h)]);
+          }
+#define FLR_SX(TA, TB)                                                                              \
+  _Pragma("unroll") for (int i = 0; i < MS; ++i) _Pragma("unroll") for (int j = 0; j < NS; ++j) \
+      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][TA], fb[j][TB], acc[i][j], 0, 0, 0);
+        // product-major, small terms first (term 0 = hi, 1 = mid, 2 = lo)
+        FLR_SX(1, 1) FLR_SX(0, 2) FLR_SX(2, 0) FLR_SX(0, 1) FLR_SX(1, 0) FLR_SX(0, 0)
+#undef FLR_SX
+      }
+  };
+  const int ntile = rend > rbeg ? (rend - rbeg + BK - 1) / BK : 0;
+  if (ntile > 0) {
+    const int rlast = rbeg + (ntile - 1) * BK;
+    load(rbeg);
+    split_all();
+    write_all();
+    load(std::min(rbeg + BK, rlast));
+    __syncthreads();
+    // one K-tile: the MFMAs of tile t from the LDS images, the split of tile t+1
+    // between them, its stash, then the global loads of tile t+2 into the
+    // registers just freed (clamped past the last tile: duplicates)
+    auto tile_body = [&](int t) {
+      const int r0 = rbeg + t * BK;
+      compute_tile();
+      split_all();
+      __syncthreads();  // every wave's fragment reads of tile t are done
+      write_all();
+      load(std::min(r0 + 2 * BK, rlast));
+      __syncthreads();
+    };
+    for (int t = 0; t < ntile; ++t) tile_body(t);
+  }
+  const TileOffs<MS, NS> off = sub_tiles<MS, NS>(wm, wn);
+  store_tiles<Plan, MS, NS>(pl, S, part, k, split, m0, n0, h, l32, M, N, acc, off);
+  if constexpr (has_sq<Plan>::value) {
+    if (S == 1 && pl.sq) {
+      __shared__ double red[THREADS / 64];
+      store_sumsq(pl, k, bx, by, m0, n0, h, l32, M, N, acc, off, red);
+    }
+  }
+}
+
+template <class Plan>
+__global__ void treduce_kernel(const Plan pl, int S, const float* __restrict__ part) {
+  // grid (cdiv(M*N, 256), K): one client per grid row, 32-bit index math
+  const int M = pl.M(), N = pl.N(), K = pl.g.Kc;
+  const int k = blockIdx.y;
+  const int e = blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t MN = (int64_t)M * N;
+  float v = 0.f;
+  if (e < MN) {
+    const int m = e / N, n = e - m * N;
+    const int64_t idx = k * MN + e;
+    v = part[idx];
+    for (int s = 1; s < S; ++s) v += part[(int64_t)s * MN * K + idx];
+    pl.store(k, m, n, v);
+  }
+  if constexpr (has_sq<Plan>::value) {
+    if (pl.sq) {  // this block's clip-norm partial (slot = blockIdx.x)
+      __shared__ double red[4];
+      const double t = block_sumsq((double)v * (double)v, red);
+      if (threadIdx.x == 0) pl.sq[(int64_t)k * pl.sq_ld + blockIdx.x] = t;
+    }
+  }
+}
+
+#ifdef FLR_ABLATION
+}  // namespace convt
+}  // namespace flr
+#include "conv_t_ablation.h"  // the tools build's kernel forms: they use the epilogue above
+namespace flr {
+namespace convt {
+#endif
+
+// Split-K count from the PER-CLIENT problem only (never the client count K):
+// a client's reduction order — and so its trained weights — must not depend
+// on how many clients share its GPU (bit-identical results at 1/2/4/8 GPUs).
+// 16 tiles per client = the 2048-workgroup target at the nominal 128 clients.
+// min_kt: fewest K-tiles a split may keep (8 for the convolutions; the batched
+// GEMMs read FLR_BGEMM_MINKT, default 32: 8 cost 1.7 ms per C3 round in split-K partials and reduce passes).
+inline int choose_splits(int M, int N, int R, int /*K*/, int sub = 1, int min_kt = 8) {
+  const int tiles = cdiv(M, BM) * cdiv(N, BN) / sub;
+  const int ktiles = cdiv(R, BK);
+  int S = 1;
+  while (S < 16 && tiles * S < 16 && ktiles / (2 * S) >= min_kt) S *= 2;
+  return S;
+}
+
+inline int bgemm_min_kt() {
+  static const int v = [] {
+    const char* e = flr::knob("FLR_BGEMM_MINKT");
+    const int x = e ? atoi(e) : 0;
+    return x >= 1 && x <= 64 ? x : 32;
+  }();
+  return v;
+}
+
+// Fewest K-tiles per conv split-K part.  32 (measured per layer against 8 and 16,
+// tools/conv_bench.py): a workgroup's unhidden prologue (first load, split,
+// barrier) amortises over more K-tiles; the l3b / l4 forward and dgrad gain the
+// most.  FLR_CONV_MINKT overrides (A/B timing).
+inline int conv_min_kt() {
+  static const int v = [] {
+    const char* e = flr::knob("FLR_CONV_MINKT");
+    const int x = e ? atoi(e) : 0;
+    return x >= 1 && x <= 256 ? x : 32;
+  }();
+  return v;
+}
+
+// Stride-1 dgrad (one class: the forward's GEMM shape, transposed) takes the
+// forward's split rule unless FLR_DGRAD_MINKT1 overrides it (A/B timing).
+inline int dgrad_min_kt1() {
+  static const int v = [] {
+    const char* e = flr::knob("FLR_DGRAD_MINKT1");
+    const int x = e ? atoi(e) : 0;
+    return x >= 1 && x <= 256 ? x : 0;
+  }();
+  return v ? v : conv_min_kt();
+}
+
+// Strided dgrad classes (FLR_DGRAD_MINKT2 overrides 8 for A/B timing).
+inline int dgrad_min_kt2() {
+  static const int v = [] {
+    const char* e = flr::knob("FLR_DGRAD_MINKT2");
+    const int x = e ? atoi(e) : 0;
+    return x >= 1 && x <= 256 ? x : 8;
+  }();
+  return v;
+}
+
+template <class Plan>
+inline int plan_min_kt(const Plan& pl) {
+  if (std::is_base_of<BGemmArgs, Plan>::value) return bgemm_min_kt();
+  // a strided dgrad's parity class has few tiles per client (l3a: one 128 x 128
+  // tile): it keeps the deeper split-K, or the launch runs ~128 workgroups on 256 CUs
+  if constexpr (std::is_same<Plan, DgradT>::value) return pl.g.stride == 1 ? dgrad_min_kt1() : dgrad_min_kt2();
+  return conv_min_kt();
+}
+
+template <class Plan>
+size_t splits_bytes(const Plan& pl) {  // enough for any sub-tile count (1, 2, 3, 4)
+  int S = 1;
+  for (int sub : {1, 2, 3, 4}) S = std::max(S, choose_splits(pl.M(), pl.N(), pl.R(), pl.g.Kc, sub, plan_min_kt(pl)));
+  return S > 1 ? (size_t)S * pl.g.Kc * pl.M() * pl.N() * sizeof(float) : 0;
+}
+
+// Workgroup tile: 64 x 64 (MS = NS = 1: 4 waves of 32 x 32, 4 workgroups/CU)
+// or 128 x 128 (MS = NS = 2: each wave 64 x 64, its A and B fragments — and
+// their bf16 splits — reused twice; 2 workgroups/CU).  Measured per ResNet-18
+// layer on MI355X (tools/conv_bench.py): 128 x 128 wins where both dimensions
+// allow it and the tile still has work — a reduction of >= 512 or more than
+// 128 x 512 outputs per client; 64 x 64 everywhere else.
+// FLR_CONV_TILE=11|21|12|22 forces a shape (read per launch, for A/B runs).
+inline int tile_choice(int M, int N, int R) {
+  const char* e = flr::knob("FLR_CONV_TILE");
+  const int forced = e ? atoi(e) : 0;
+  if (forced == 11) return 11;
+  if (forced == 21 && M % 128 == 0) return 21;
+  if (forced == 12 && N % 128 == 0) return 12;
+  const bool big = M % 128 == 0 && N % 128 == 0;
+  if (forced == 22 && big) return 22;
+  if (forced == 0 && big && (R >= 512 || (int64_t)M * N > 128 * 512)) return 22;
+  return 11;
+}
+
+template <class Plan, int MS, int NS>
+int launch_tiles(const Plan& pl, void* ws, size_t ws_bytes, hipStream_t st, const char* name, int split_sub = 0) {
+  const int M = pl.M(), N = pl.N(), R = pl.R(), K = pl.g.Kc;
+  // split_sub: the sub-tile count the split-K choice is made for (0: this tile's);
+  // a launch on smaller tiles with the default tile's split count computes the
+  // same sums in the same order (fill_tile below)
+  int S = choose_splits(M, N, R, K, split_sub > 0 ? split_sub : MS * NS, plan_min_kt(pl));
+  if (S > 1 && (!ws || ws_bytes < (size_t)S * K * M * N * sizeof(float))) {
+    // a clip-norm launch must write the slots sq_slots() promised: no silent fallback
+    if constexpr (has_sq<Plan>::value) {
+      if (pl.sq) return FLR_ERR_WORKSPACE;
+    }
+    S = 1;
+  }
+  const dim3 grid((unsigned)cdiv(N, BN * NS), (unsigned)cdiv(M, BM * MS), (unsigned)(K * S));
+  int form = gemm_form();
+  float* partp = static_cast<float*>(ws);  // split-K partials (after the planes in the pre-split form)
+#ifdef FLR_ABLATION  // the measured-slower batched-GEMM forms: tools build only
+  if constexpr (is_bgemm_t<Plan>::ta || is_bgemm_t<Plan>::tb) {
+    // batched GEMMs with a k-contiguous operand: that operand on a transposed
+    // image (coalesced 128-B row reads, conflict-free stashes; the row-major
+    // image of a quad-lane load stashes 2-way bank-conflicted)
+    if (form == 5 && bgemm_timg()) {
+      hipLaunchKernelGGL((wsgemm_kernel<Plan, MS, NS, is_bgemm_t<Plan>::ta, is_bgemm_t<Plan>::tb>), grid,
+                         dim3(THREADS), 0, st, pl, S, static_cast<float*>(ws), xcd_remap());
+      form = -1;
+    }
+  }
+  if constexpr (std::is_base_of<BGemmArgs, Plan>::value && MS == 2 && NS == 2) {
+    if (form == 5 && bgemm_presplit()) {
+      const size_t pa_b = (ps_plane_bytes(K, M, R) + 255) / 256 * 256;
+      const size_t pb_b = (ps_plane_bytes(K, N, R) + 255) / 256 * 256;
+      const size_t need = pa_b + pb_b + (S > 1 ? (size_t)S * K * M * N * sizeof(float) : 0);
+      // the planes' byte offsets must fit the 31-bit buffer voffset
+      if (ws && ws_bytes >= need && pa_b < (size_t(1) << 31) && pb_b < (size_t(1) << 31)) {
+        __bf16* pa = static_cast<__bf16*>(ws);
+        __bf16* pb = reinterpret_cast<__bf16*>(static_cast<char*>(ws) + pa_b);
+        partp = reinterpret_cast<float*>(static_cast<char*>(ws) + pa_b + pb_b);
+        const int Mp = (int)ps_pad(M, PS_ROWS), Np = (int)ps_pad(N, PS_ROWS), Rp = (int)ps_pad(R, BK);
+        auto pgrid = [](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384))); };
+        hipLaunchKernelGGL((presplit_kernel<Plan::AMODE>), pgrid((int64_t)K * Mp * Rp / 8), dim3(THREADS), 0, st, pl.a,
+                           pl.a_k, pl.a_m, pl.a_r, K, M, R, Mp, Rp, pa);
+        hipLaunchKernelGGL((presplit_kernel<Plan::BMODE>), pgrid((int64_t)K * Np * Rp / 8), dim3(THREADS), 0, st, pl.b,
+                           pl.b_k, pl.b_n, pl.b_r, K, N, R, Np, Rp, pb);
+        hipLaunchKernelGGL((psgemm_kernel<Plan>), grid, dim3(THREADS), 0, st, pl, S, partp, xcd_remap(), pa, pb, Mp,
+                           Np, Rp);
+        form = -1;
+      }
+    }
+  }
+  if constexpr (dma_ok<Plan>::value && MS == 2 && NS == 2) {
+    if (form == 5 && bgemm_dma()) {
+      hipLaunchKernelGGL((dsgemm_kernel<Plan>), grid, dim3(THREADS), 0, st, pl, S, static_cast<float*>(ws),
+                         xcd_remap());
+      form = -1;
+    }
+  }
+#endif
+  if constexpr (has_k8<Plan>::value) {
+#ifdef FLR_ABLATION
+    if constexpr (MS == 2 && NS == 2) {
+      const char* ae = flr::knob("FLR_SG_ABL");  // timing ablations of the main loop (tools build only)
+      const int abl = ae ? atoi(ae) : 0;
+#define FLR_SG_ABL_CASE(A)                                                                                  \
+  if (form == 5 && abl == A) {                                                                               \
+    hipLaunchKernelGGL((sgemm_kernel<Plan, MS, NS, A>), grid, dim3(THREADS), 0, st, pl, S,               \
+                       static_cast<float*>(ws), xcd_remap());                                                \
+    form = -1;                                                                                               \
+  }
+      FLR_SG_ABL_CASE(1) FLR_SG_ABL_CASE(2) FLR_SG_ABL_CASE(3) FLR_SG_ABL_CASE(4) FLR_SG_ABL_CASE(8)
+      FLR_SG_ABL_CASE(10) FLR_SG_ABL_CASE(16) FLR_SG_ABL_CASE(11) FLR_SG_ABL_CASE(15) FLR_SG_ABL_CASE(23)
+#undef FLR_SG_ABL_CASE
+    }
+#endif
+    if (form == 5) {
+      hipLaunchKernelGGL((sgemm_kernel<Plan, MS, NS>), grid, dim3(THREADS), 0, st, pl, S, static_cast<float*>(ws),
+                         xcd_remap());
+      form = -1;
+    }
+  }
+  if constexpr (std::is_same<Plan, WgtT<true>>::value || std::is_same<Plan, WgtT<false>>::value) {
+    if (form == 5) {
+      hipLaunchKernelGGL((wsgemm_kernel<Plan, MS, NS, true, true>), grid, dim3(THREADS), 0, st, pl, S,
+                         static_cast<float*>(ws), xcd_remap());
+      form = -1;
+    }
+  }
+  if (form == 5) form = 2;  // plans without k8 loads
+  switch (form) {  // every form keeps each accumulator's product order: results do not depend on it
+    case -1:
+      break;
+    case 0:
+      hipLaunchKernelGGL((tgemm_kernel<Plan, MS, NS, 0>), grid, dim3(THREADS), 0, st, pl, S,
+                         static_cast<float*>(ws), xcd_remap(), mfma_prio());
+      break;
+#ifdef FLR_ABLATION
+    case 1:
+      hipLaunchKernelGGL((tgemm_kernel<Plan, MS, NS, 1>), grid, dim3(THREADS), 0, st, pl, S,
+                         static_cast<float*>(ws), xcd_remap(), mfma_prio());
+      break;
+    case 3:
+      hipLaunchKernelGGL((tgemm_kernel<Plan, MS, NS, 3>), grid, dim3(THREADS), 0, st, pl, S,
+                         static_cast<float*>(ws), xcd_remap(), mfma_prio());
+      break;
+    case 4:
+      hipLaunchKernelGGL((tgemm_kernel<Plan, MS, NS, 4>), grid, dim3(THREADS), 0, st, pl, S,
+                         static_cast<float*>(ws), xcd_remap(), mfma_prio());
+      break;
+#endif
+    default:
+      hipLaunchKernelGGL((tgemm_kernel<Plan, MS, NS, 2>), grid, dim3(THREADS), 0, st, pl, S,
+                         static_cast<float*>(ws), xcd_remap(), mfma_prio());
+  }
+  int rc = launch_status(name);
+  if (rc != FLR_OK || S == 1) return rc;
+  const int64_t mn = (int64_t)M * N;
+  hipLaunchKernelGGL(treduce_kernel<Plan>, dim3((unsigned)((mn + 255) / 256), (unsigned)K), dim3(256), 0, st, pl, S,
+                     static_cast<const float*>(partp));
+  return launch_status(name);
+}
+
+// Tile code 10 * MS + NS.  Besides the square shapes above, the tap-major
+// convolutions take 64 x 192 / 192 x 64 (13 / 31) and 64 x 256 / 256 x 64
+// (14 / 41): a 64-row operand (layer1's 64 channels) then feeds three or four
+// MFMA sub-tiles per fragment read instead of one or two (LDS: five sub-tiles
+// of bf16 images, still two workgroups per CU).
+template <class Plan>
+constexpr bool wide_tiles() {
+  return std::is_same<Plan, FwdT>::value || std::is_same<Plan, DgradT>::value ||
+         std::is_same<Plan, WgtT<true>>::value || std::is_same<Plan, WgtT<false>>::value;
+}
+
+template <class Plan>
+inline int plan_tile(const Plan& pl) {
+  const int M = pl.M(), N = pl.N(), R = pl.R();
+  const char* e = flr::knob("FLR_CONV_TILE");
+  const int forced = e ? atoi(e) : 0;
+  if (forced) {  // A/B timing: any shape that leaves no sub-tile empty
+    const int ms = forced / 10, ns = forced % 10;
+    const bool ok = ms >= 1 && ns >= 1 && ms * ns <= 4 && (wide_tiles<Plan>() || (ms <= 2 && ns <= 2)) &&
+                    M > 64 * (ms - 1) && N > 64 * (ns - 1);
+    if (ok) return forced;
+  }
+  int tile = tile_choice(M, N, R);
+  // dgrad with 64 input channels (layer1): 64 x 128 tiles, the A fragment feeding
+  // two B sub-tiles (measured 178 -> 147 us at l1)
+  if (std::is_same<Plan, DgradT>::value && tile == 11 && M == 64 && N % 128 == 0) tile = 12;
+  return tile;
+}
+
+// Clip-norm partial slots per client a WgtT launch writes (the tile count at
+// split-K 1, else one per 256-value treduce block), under the launch's own
+// tile and split choice — given a workspace of splits_bytes(pl).
+template <class Plan>
+int sq_slots(const Plan& pl) {
+  const int M = pl.M(), N = pl.N(), R = pl.R();
+  const int tile = plan_tile(pl);
+  const int ms = tile / 10, ns = tile % 10;
+  const int S = choose_splits(M, N, R, pl.g.Kc, ms * ns, plan_min_kt(pl));
+  if (S == 1) return cdiv(N, BN * ns) * cdiv(M, BM * ms);
+  return (int)(((int64_t)M * N + 255) / 256);
+}
+
+// Narrow-N tiles (sgemm_body NAR) for the conv forward / data gradient whose GEMM has
+// at most 32 columns (the l4 layers at 32 x 32 inputs: B * 1 * 1); FLR_CONV_NARROW=0:
+// the 64-wide tiles (A/B, read per launch).
+inline bool conv_narrow() {
+  const char* e = flr::knob("FLR_CONV_NARROW");
+  return !(e && e[0] == '0');
+}
+template <class Plan>
+int launch_narrow(const Plan& pl, void* ws, size_t ws_bytes, hipStream_t st, const char* name) {
+  const int M = pl.M(), N = pl.N(), R = pl.R(), K = pl.g.Kc;
+  int S = choose_splits(M, N, R, K, 2, plan_min_kt(pl));
+  if (S > 1 && (!ws || ws_bytes < (size_t)S * K * M * N * sizeof(float))) S = 1;
+  const dim3 grid((unsigned)cdiv(N, BN), (unsigned)cdiv(M, 2 * BM), (unsigned)(K * S));
+  hipLaunchKernelGGL((sgemm_kernel<Plan, 2, 1, 0, true>), grid, dim3(THREADS), 0, st, pl, S,
+                     static_cast<float*>(ws), xcd_remap());
+  int rc = launch_status(name);
+  if (rc != FLR_OK || S == 1) return rc;
+  const int64_t mn = (int64_t)M * N;
+  hipLaunchKernelGGL(treduce_kernel<Plan>, dim3((unsigned)((mn + 255) / 256), (unsigned)K), dim3(256), 0, st, pl, S,
+                     static_cast<const float*>(ws));
+  return launch_status(name);
+}
+
+// Small client counts (K/G clients per GPU at G = 8: 16 at C3) leave the
+// default tiles' grids below one wave of the chip: layer2 / layer3 of ResNet-18
+// launch 4 workgroups of 128 x 128 per client.  Forward and data-gradient
+// launches whose grid would hold fewer than FILL_WG workgroups then run on
+// 64 x 64 tiles with the DEFAULT tile's split-K count: every output element is
+// the same K-tile / k-step / product sequence, so the result is bit-identical
+// to the default tiles (and the model to the one at G = 1).  The weight
+// gradients keep their tiles: their clip-norm partial slots follow the tile.
+// FLR_CONV_FILL=0: off (A/B, read per launch).
+constexpr int FILL_WG = 512;  // two 128 x 128 workgroups per CU on 256 CUs
+inline bool conv_fill() {
+  const char* e = flr::knob("FLR_CONV_FILL");
+  return !(e && e[0] == '0');
+}
+template <class Plan>
+bool fill_tile(const Plan& pl, int tile) {
+  if constexpr (!(std::is_same<Plan, FwdT>::value || std::is_same<Plan, DgradT>::value)) {
+    return false;
+  } else {
+    const int ms = tile / 10, ns = tile % 10;
+    if (ms * ns == 1 || !conv_fill()) return false;
+    const int M = pl.M(), N = pl.N(), R = pl.R();
+    const int S = choose_splits(M, N, R, pl.g.Kc, ms * ns, plan_min_kt(pl));
+    const int64_t wg = (int64_t)pl.g.Kc * cdiv(M, BM * ms) * cdiv(N, BN * ns) * S;
+    return wg < FILL_WG;
+  }
+}
+
+template <class Plan>
+int launch(const Plan& pl, void* ws, size_t ws_bytes, hipStream_t st, const char* name) {
+  if (pl.R() == 0 && !std::is_same<Plan, DgradT>::value) return FLR_OK;  // a dgrad class with no tap stores zeros
+  if constexpr (std::is_same<Plan, FwdT>::value || std::is_same<Plan, DgradT>::value) {
+    if (pl.N() <= 32 && pl.M() % (2 * BM) == 0 && pl.R() > 0 && gemm_form() == 5 && conv_narrow()) {
+      // a narrow launch under one wave of the chip (few clients per GPU): the 64 x 64
+      // tiles with the narrow tiles' split count — twice the workgroups, the same bits
+      const int S = choose_splits(pl.M(), pl.N(), pl.R(), pl.g.Kc, 2, plan_min_kt(pl));
+      if (conv_fill() && (int64_t)pl.g.Kc * cdiv(pl.M(), 2 * BM) * S < FILL_WG / 2)
+        return launch_tiles<Plan, 1, 1>(pl, ws, ws_bytes, st, name, 2);
+      return launch_narrow(pl, ws, ws_bytes, st, name);
+    }
+  }
+  const int tile = plan_tile(pl);
+  if (fill_tile(pl, tile)) return launch_tiles<Plan, 1, 1>(pl, ws, ws_bytes, st, name, (tile / 10) * (tile % 10));
+  if constexpr (wide_tiles<Plan>()) {
+    switch (tile) {
+      case 13: return launch_tiles<Plan, 1, 3>(pl, ws, ws_bytes, st, name);
+      case 31: return launch_tiles<Plan, 3, 1>(pl, ws, ws_bytes, st, name);
+      case 14: return launch_tiles<Plan, 1, 4>(pl, ws, ws_bytes, st, name);
+      case 41: return launch_tiles<Plan, 4, 1>(pl, ws, ws_bytes, st, name);
+      default: break;
+    }
+  }
+  switch (tile) {
+    case 21: return launch_tiles<Plan, 2, 1>(pl, ws, ws_bytes, st, name);
+    case 12: return launch_tiles<Plan, 1, 2>(pl, ws, ws_bytes, st, name);
+    case 22: return launch_tiles<Plan, 2, 2>(pl, ws, ws_bytes, st, name);
+    default: return launch_tiles<Plan, 1, 1>(pl, ws, ws_bytes, st, name);
+  }
+}
+
+inline bool shape_ok(int64_t Cin, int64_t Cout) { return Cin % 64 == 0 && Cout % 64 == 0; }
+
+inline bool args_ok(int64_t K, int64_t B, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int64_t KH, int64_t KW,
+                    int64_t stride, int64_t pad) {
+  if (!conv::geom_ok(K, B, Cin, H, W, Cout, KH, KW, stride, pad) || !shape_ok(Cin, Cout)) return false;
+  // byte offsets inside one client's buffer view must fit the 31-bit voffset
+  if (!(B * K * Cin * H * W * 4 < (int64_t(1) << 31) && B * K * Cout * H * W * 4 < (int64_t(1) << 31) &&
+        KH * KW * Cin * Cout * 4 < (int64_t(1) << 31)))
+    return false;
+  // the kernels decode taps by rectangle arithmetic (true for any stride <= 4
+  // conv whose live rows / columns are contiguous: every ResNet shape)
+  if (stride > 4) return false;
+  const conv::Geom g = conv::make_geom(K, B, Cin, H, W, Cout, KH, KW, stride, pad);
+  if (!g.rect.ok) return false;
+  DgradT cls[MAX_CLASSES];
+  const int nc = dgrad_classes(g, cls);
+  for (int c = 0; c < nc; ++c)
+    if (!cls[c].crect.ok) return false;
+  return true;
+}
+
+}  // namespace convt
+}  // namespace flr

@@ -322,3 +322,58 @@ def test_fill_tiles_bit_identical(cuda, shape, knob):
     for a, b in zip(*outs):
         assert not torch.isnan(a).any()
         assert torch.equal(a, b)
+
+
+TILE_CODES = (12, 21, 22, 13, 31, 14, 41)
+
+
+@pytest.mark.parametrize("form", [None, "pipe"])
+@pytest.mark.parametrize("shape", [(2, 16, 256, 4, 4, 256, 1, 1, 0), (2, 8, 128, 4, 4, 192, 3, 1, 1)],
+                         ids=["1x1-256", "3x3-ragged"])
+def test_forced_tiles_bit_identical(cuda, shape, form, knob):
+    """One store routine serves every workgroup tile (FLR_CONV_TILE 11, 12, 21,
+    22, 13, 31, 14, 41) of the pipelined, split-at-stash and transposed-image
+    kernels: forward, data gradient and weight gradient give the 64 x 64
+    tiles' bits at every forced shape, and the clip-norm partials (whose slot
+    count follows the tile) the same fp64 sum within 1e-12.  All three
+    reductions are at most 2016 long, so the split-K count is 1 at every
+    sub-tile count; a code the plan rejects (ragged edges) runs the default
+    tile.  FLR_CONV_FILL=0 keeps the forced tile for the small grids."""
+    from flr import _capi
+    from flr.nn import _stream, _workspace_t
+    if form:
+        knob("FLR_GEMM", form)
+    knob("FLR_CONV_FILL", "0")
+    K, B, Cin, H, W, Cout, KS, stride, pad = shape
+    g = torch.Generator(device="cpu").manual_seed(sum(shape) + 17)
+    Ho, Wo = (H + 2 * pad - KS) // stride + 1, (W + 2 * pad - KS) // stride + 1
+    x = torch.randn(K * Cin, B, H, W, generator=g).to(cuda)
+    dy = torch.randn(K * Cout, B, Ho, Wo, generator=g).to(cuda)
+    wt = (torch.randn(K, KS, KS, Cin, Cout, generator=g) * 0.1).to(cuda)
+    geom = (K, B, Cin, H, W, Cout, KS, KS, stride, pad)
+    ws, nb = _workspace_t(geom, cuda)
+    wsp = None if ws is None else ws.data_ptr()
+
+    def run(code):
+        knob("FLR_CONV_TILE", str(code))
+        y = torch.full((K * Cout, B, Ho, Wo), float("nan"), device=cuda)
+        _capi.call("flr_conv2d_fwd_t", x.data_ptr(), wt.data_ptr(), y.data_ptr(), *geom, wsp, nb, _stream(x))
+        dx = torch.full_like(x, float("nan"))
+        _capi.call("flr_conv2d_bwd_data_t", dy.data_ptr(), wt.data_ptr(), dx.data_ptr(), *geom, wsp, nb, _stream(x))
+        n = int(_capi.lib().flr_conv2d_bwd_weight_t_sq_slots(*geom))
+        assert n > 0
+        dw = torch.full((K, KS, KS, Cin, Cout), float("nan"), device=cuda)
+        sq = torch.full((K, n), float("nan"), dtype=torch.float64, device=cuda)
+        _capi.call("flr_conv2d_bwd_weight_t_sq", x.data_ptr(), dy.data_ptr(), dw.data_ptr(), *geom, 1,
+                   sq.data_ptr(), n, wsp, nb, _stream(x))
+        torch.cuda.synchronize()
+        return y.cpu(), dx.cpu(), dw.cpu(), sq.sum(1).cpu()
+
+    ref = run(11)
+    for t in ref:
+        assert not torch.isnan(t).any()
+    for code in TILE_CODES:
+        got = run(code)
+        for which, a, b in zip(("y", "dx", "dw_t"), ref, got):
+            assert torch.equal(a, b), (code, which)
+        assert torch.allclose(got[3], ref[3], rtol=1e-12, atol=0), (code, got[3], ref[3])

@@ -19,7 +19,7 @@ def sha(t: torch.Tensor) -> str:
 
 
 def main():
-    dev = torch.device("cuda")
+    dev = torch.device("cuda", torch.cuda.current_device())  # indexed: the trainers compare devices
     K = int(os.environ.get("K", 16))
     eng = RoundEngine(ModelSpec(), RoundConfig(num_clients=K, num_attackers=K // 5),
                       TrainConfig(local_steps=5), dev)
