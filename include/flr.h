@@ -146,7 +146,16 @@ int flr_pairwise_l2_reference_tap(const float* X, int64_t K, int64_t P, int64_t 
  * (FLR_TC_DEFER_DEAD): its slab is read from gdead at the same training-order
  * offset, negated on rows k < nneg — the values flr_resnet_gru_fill_dead
  * writes, so D is bit-identical to the call on the filled X.  No dead column
- * may lie in the last P mod 8 (read from X): FLR_ERR_ARG. */
+ * may lie in the last P mod 8 (read from X): FLR_ERR_ARG.
+ * A 3 x 3 block at off % 8 == 0 with Cout Cin % 8 == 0 whose live taps are the
+ * centre alone (mask 0x1EF) or taps 4, 5, 7, 8 (mask 0x04F) runs as a dead
+ * region (part 0 of 1): only its live coordinates are
+ * rewritten, its dead ones come from one shared stream of g + g that the pairs
+ * with exactly one negated row add in the chain's order, and the other pairs
+ * skip them (fl(g - g) = +0; a dead value of g that is not finite makes those
+ * pairs NaN, as on the filled X).  Any other block is expanded from gdead as
+ * before; the knob FLR_REF_DEAD_SKIP=0 (flr_set_knob) expands every block.  The
+ * same bits either way. */
 int flr_pairwise_l2_reference_tap_dead(const float* X, int64_t K, int64_t P, int64_t ldx,
                                        const int64_t* taps, int64_t ntaps, const uint64_t* dead,
                                        const float* gdead, int64_t nneg, double* D, void* ws,

@@ -39,6 +39,11 @@
 //  * chain c = the XCD (blockIdx % 8): an XCD's L2 holds only its own chain's
 //    streams.  40 KB of LDS per workgroup: four per CU, one wave per SIMD.
 // Chains longer than the segment carry their partial sums in A between segments.
+//  * Dead regions (flr_pairwise_l2_reference_tap_dead): a 3 x 3 block whose
+//    dead taps equal +-g in every row is its own chain launch (run_chains) over
+//    two streams, the rows' live taps and one shared row of g + g (DeadPlan,
+//    dead_chunk, ref_chain_dead_kernel); a pair of two rows of the same sign
+//    skips the dead steps, fma(+0, +0, s) = s.
 #include <cstdint>
 #include <type_traits>
 #include <utility>
@@ -210,15 +215,43 @@ constexpr int TAP_ROWS = 288;  // LDS tile rows (tap, input channel): CI = TAP_R
 // the dense write enumeration divides item indices < TAP_CO * TAP_ROWS through
 // a float reciprocal: exact while they stay far below 2^24 / (the divisor)
 static_assert(TAP_CO * TAP_ROWS < (1 << 14), "dense write items exact in fp32");
-template <int KKT, bool VEC>  // KKT: 9, 1, or 0 = KK at run time; VEC: 16-B aligned tile rows
+
+// A dead-tap region (run_chains): a 3 x 3 block at off % 8 == 0 whose dead
+// taps every row shares (g, negated on rows < nneg).  Chain c's step s of the
+// block (coordinate off + 8 s + c) has tap (c - s) mod 9, because 8 = -1
+// (mod 9): the block's mask with period 9, at a phase that depends on the chain.
+// Each chain is laid out on virtual steps v = s + 8 - c, so that every chain's
+// period m = v / 9 visits the taps 8, 7, .. 0 in that order, and split into two
+// streams: the live steps Xl[k][c][m NL + rank of the tap among the live ones]
+// and the dead ones T[c][m ND + rank among the dead ones] = g + g, one row.
+// The slots before a chain's first step and after its last are 0 in both
+// streams: fma(0, 0, s) = s, the identity the padded chain streams rely on.
+struct DeadPlan {
+  int on;              // the compact form (tap_chain_kernel) / a dead region
+  int nl, nd;          // live and dead taps
+  uint64_t tap, rank;  // 4-bit fields: tap[n] = the n-th live tap, rank[t] = tap t's rank among its kind
+};
+__host__ __device__ inline int dead_nib(uint64_t v, int n) { return (int)((v >> (4 * n)) & 15); }
+// slot of block coordinate rel (tap t) in its stream of n taps per period
+__host__ __device__ inline int64_t dead_slot(int64_t rel, int t, int n, uint64_t rank) {
+  const int64_t c = rel & 7, s = rel >> 3;
+  return (s + 8 - c) / 9 * n + dead_nib(rank, t);
+}
+
+// CMP: a dead region's compact form (dp): the tile holds the live taps alone,
+// TAP_ROWS / nl input channels of each, so that an output channel's run stays
+// as long in the live stream as a whole block's run is in the plain one
+template <int KKT, bool VEC, bool CMP = false>  // KKT: 9, 1, or 0 = KK at run time; VEC: 16-B aligned tile rows
 __global__ __launch_bounds__(256) void tap_chain_kernel(const float* __restrict__ X, int64_t ldx, int64_t off,
                                                         int Cout, int Cin, int KKr, int64_t r0, int64_t steps,
                                                         int64_t ldc, float* __restrict__ Xc,
-                                                        const float* __restrict__ gdead, uint64_t dead, int nneg) {
+                                                        const float* __restrict__ gdead, uint64_t dead, int nneg,
+                                                        const DeadPlan dp) {
   constexpr int TCO = TAP_CO, TROWS = TAP_ROWS;
   __shared__ float tile[TROWS][TCO + 1];
   const int KK = KKT > 0 ? KKT : KKr;
-  const int CI = TROWS / KK;
+  const int NR = CMP ? dp.nl : KK;  // tile rows per input channel: the taps it holds
+  const int CI = TROWS / NR;
   const int nci_t = (Cin + CI - 1) / CI, ntiles = (int)gridDim.x;
   // XCD-contiguous tile numbering: XCD x = blockIdx % 8 takes tiles
   // [x * ntiles / 8, (x + 1) * ntiles / 8)
@@ -235,7 +268,8 @@ __global__ __launch_bounds__(256) void tap_chain_kernel(const float* __restrict_
   auto is_dead = [&](int t) { return t < 64 && ((dead >> t) & 1); };
   auto src = [&](int t) { return is_dead(t) ? grow : row; };
   auto sgn = [&](int t) { return is_dead(t) ? gs : 1.f; };  // (x * 1 == x, -x exact)
-  const int nrows = KK * CI;
+  const int nrows = NR * CI;
+  auto tap_of = [&](int tr) { return CMP ? dead_nib(dp.tap, tr) : tr; };  // tile row group tr's tap
   // load: tile row r = t * CI + ci, column = output channel; every load of a
   // thread issued before its LDS stores
   if constexpr (VEC) {  // nco_v == TCO: a row is TCO / 4 pieces of 16 B
@@ -245,11 +279,11 @@ __global__ __launch_bounds__(256) void tap_chain_kernel(const float* __restrict_
     f32x4 v[IT];
 #pragma unroll
     for (int q = 0; q < IT; ++q) {
-      const int r = rr + RPP * q, t = r / CI, ci = r - t * CI;
+      const int r = rr + RPP * q, tr = r / CI, ci = r - tr * CI, t = tap_of(tr);
       const int64_t e = ((int64_t)t * Cin + ci0 + ci) * Cout + co0 + 4 * sub;
       if (!(r < nrows && ci < nci))
         v[q] = f32x4{0.f, 0.f, 0.f, 0.f};
-      else if (is_dead(t))  // the global vector, re-read by every client: cached loads
+      else if (!CMP && is_dead(t))  // the global vector, re-read by every client: cached loads
         v[q] = *reinterpret_cast<const f32x4*>(grow + e) * gs;
       else
         v[q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(row + e));
@@ -263,11 +297,29 @@ __global__ __launch_bounds__(256) void tap_chain_kernel(const float* __restrict_
     }
   } else {
     for (int e = threadIdx.x; e < nrows * TCO; e += 256) {
-      const int co = e % TCO, r = e / TCO, t = r / CI, ci = r % CI;
-      if (ci < nci && co < nco_v) tile[r][co] = src(t)[((int64_t)t * Cin + ci0 + ci) * Cout + co0 + co] * sgn(t);
+      const int co = e % TCO, r = e / TCO, t = tap_of(r / CI), ci = r % CI;
+      if (ci < nci && co < nco_v)
+        tile[r][co] = (CMP ? row : src(t))[((int64_t)t * Cin + ci0 + ci) * Cout + co0 + co] * (CMP ? 1.f : sgn(t));
     }
   }
   __syncthreads();
+  if constexpr (CMP) {
+    // the live coordinates alone, at their slots of the live stream (Xc: the
+    // region's streams): output channel co's items (ci, live tap), tap
+    // fastest, dealt to the lanes with a stride of 8 — with one live tap a
+    // chain's coordinates are 8 input channels apart, so consecutive lanes
+    // write consecutive slots of one chain
+    const int per = nci * dp.nl, n = nco_v * per, p8 = per / 8;
+    const bool deal = per % 8 == 0;
+    float* outl = Xc + (int64_t)k * 8 * ldc;
+    for (int i = threadIdx.x; i < n; i += 256) {
+      const int co = i / per, l = i - co * per, q = deal ? 8 * (l % p8) + l / p8 : l;
+      const int ci = q / dp.nl, lt = q - ci * dp.nl, t = dead_nib(dp.tap, lt);
+      const int64_t rel = ((int64_t)(co0 + co) * Cin + ci0 + ci) * KK + t;
+      outl[(rel & 7) * ldc + dead_slot(rel, t, dp.nl, dp.rank)] = tile[lt * CI + ci][co];
+    }
+    return;
+  }
   // write: output channel co's run [u0, u0 + nci * KK) (at most 288
   // coordinates: 38 steps per chain), clipped to the segment
   // [8 r0, 8 (r0 + steps)), chain-major: a wave writes consecutive steps of
@@ -470,6 +522,156 @@ __device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, U..
   (f(std::integral_constant<int, U>{}), ...);
 }
 
+// The slots of a region's streams that no step fills, zeroed: [0, n0) and
+// [z0, z1) of stream blockIdx.x (one launch: a pair of 2-D memsets cost more on
+// the host than the kernels they start)
+__global__ __launch_bounds__(256) void zero_slots_kernel(float* __restrict__ Xc, int64_t ldc, int n0, int64_t z0,
+                                                         int64_t z1) {
+  float* row = Xc + (int64_t)blockIdx.x * ldc;
+  const int n = n0 + (int)(z1 - z0);
+  for (int i = threadIdx.x; i < n; i += 256) row[i < n0 ? i : z0 + (i - n0)] = 0.f;
+}
+
+// The dead stream of a block (DeadPlan), once per call: T = g + g at every dead
+// coordinate's slot, and *flag raised where a dead value of g is not finite
+// (the same-kind pairs' inf - inf, which skipping their dead steps would miss:
+// ref_finish_kernel).  T is zeroed before.  Item -> (co, ci, dead tap), tap fastest.
+__global__ __launch_bounds__(256) void dead_stream_kernel(const float* __restrict__ g, int64_t off, int Cout, int Cin,
+                                                          const DeadPlan dp, int64_t ldt, float* __restrict__ T,
+                                                          int* __restrict__ flag) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (int64_t)Cout * Cin * dp.nd) return;
+  const int64_t q = idx / dp.nd;
+  const int t = dead_nib(dp.tap, (int)(idx - q * dp.nd));
+  const int64_t co = q / Cin, ci = q - co * Cin;
+  const float v = g[off + ((int64_t)t * Cin + ci) * Cout + co];
+  if ((__float_as_uint(v) & 0x7f800000u) == 0x7f800000u) *flag = 1;
+  const int64_t rel = q * 9 + t;
+  T[(rel & 7) * ldt + dead_slot(rel, t, dp.nd, dp.rank)] = v + v;
+}
+
+// A dead region's chunk: CS live steps and the dead steps between them, in
+// the chain's order (DeadPlan: periods of the taps 8 .. 0).  DM: the block's
+// dead-tap mask.  Live steps as chain_chunk (the subtraction two live steps
+// ahead of its fma, three temporaries).  A dead step is acc = fma(T, T, acc):
+// T from the stage's dead stream by ds_read_b128 of an address every mixed
+// lane shares (a broadcast); the other lanes read zeros instead (ta: their
+// address is the zero block), which leaves their sums as they are.  RQ reads
+// in flight, waited by count (LDS returns in order; the next chunk's x_j reads
+// are older than every one of them).
+template <int DM>
+struct DeadPat {
+  static constexpr int ND = __builtin_popcount(DM & 0x1ff), NL = 9 - ND;
+  static_assert(ND > 0 && NL > 0 && CS % NL == 0, "whole periods per chunk");
+  static constexpr int PPC = CS / NL;   // periods per chunk
+  static constexpr int TCH = PPC * ND;  // dead steps per chunk
+  static_assert(TCH % 4 == 0, "16-B reads of the dead stream");
+  static constexpr int NQT = TCH / 4;
+  static constexpr int NT = (TCH * 4 + 1023) / 1024;  // 1-KB DMA instructions per chunk
+  static constexpr bool dead_at(int w) { return (DM >> (8 - w)) & 1; }  // position w of a period: tap 8 - w
+  static constexpr int dead_before(int w) {
+    int n = 0;
+    for (int x = 0; x < w; ++x) n += dead_at(x) ? 1 : 0;
+    return n;
+  }
+};
+constexpr int NSTD = 4;  // ring stages of a dead region's mixed waves
+#define FLR_FMA(x) "v_fmac_f32 %[acc], %[" #x "], %[" #x "]\n\t"
+#define FLR_SUB(dd, x, j, L) \
+  "v_sub_f32_dpp %[" #dd "], %[" #x "], %[" #j "] row_newbcast:%[" #L "] row_mask:0xf bank_mask:0xf\n\t"
+template <int DM>
+__device__ __forceinline__ float dead_chunk(f32x4 xv, const f32x4 (&v)[NQ], float acc, uint32_t ta) {
+  using Pt = DeadPat<DM>;
+  static_assert(DM == 0x1EF || DM == 0x04F, "the period statements below");
+  constexpr int ND = Pt::ND, NQT = Pt::NQT;
+  constexpr int RQ = NQT < 20 ? NQT : (DM == 0x1EF ? 14 : 20);  // 16-B reads of the dead stream in flight
+  f32x4 tq[RQ];
+  float d[3];
+  auto readq = [&tq, &ta](auto Q) {  // (captures named: asm operands alone do not capture)
+    constexpr int q = decltype(Q)::value;
+    (void)tq, (void)ta;
+    asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(tq[q % RQ]) : "v"(ta), "n"(16 * q) : "memory");
+  };
+  static_for([&readq](auto Q) { readq(Q); }, std::make_integer_sequence<int, RQ>{});
+  // the first two live steps' differences; the s_nop covers the DPP
+  // read-after-write hazard on x_i (chain_chunk)
+  asm volatile("s_nop 1\n\t" FLR_SUB(da, x0, j0, L) FLR_SUB(db, x1, j1, L)
+               : [da] "=&v"(d[0]), [db] "=&v"(d[1])
+               : [x0] "v"(xv[0]), [x1] "v"(xv[1]), [j0] "v"(v[0][0]), [j1] "v"(v[0][1]), [L] "n"(0));
+  // One statement per G periods (the compiler's hazard pass puts an s_nop
+  // between dependent statements: single-instruction ones double the count).
+  // Group pg: dead values n0 .. n0 + G ND - 1 of the chunk (n / 4: the read,
+  // n % 4: its component), waited for at the group's start by count: the
+  // reads issued so far end with quad `last`.
+  constexpr int G = DM == 0x1EF ? 2 : 1;
+  static_assert(Pt::PPC % G == 0, "whole groups per chunk");
+  static_for(
+      [&tq, &d, &acc, &readq, &xv, &v](auto PP) {
+        constexpr int pg = decltype(PP)::value, p = G * pg, n0 = ND * p;
+        (void)tq, (void)d, (void)acc, (void)xv, (void)v;
+        constexpr int done = n0 / 4, last = (done + RQ < NQT ? done + RQ : NQT) - 1, need = (n0 + G * ND - 1) / 4;
+        constexpr int cnt = last - need < 15 ? last - need : 15;
+        static_assert(need <= last, "the group's reads were issued");
+#define FLR_T(n) tq[((n0 + (n)) / 4) % RQ][(n0 + (n)) % 4]
+#define FLR_T8(a, b) [t##a##0] "v"(FLR_T(b + 0)), [t##a##1] "v"(FLR_T(b + 1)), [t##a##2] "v"(FLR_T(b + 2)), \
+                     [t##a##3] "v"(FLR_T(b + 3)), [t##a##4] "v"(FLR_T(b + 4)), [t##a##5] "v"(FLR_T(b + 5)), \
+                     [t##a##6] "v"(FLR_T(b + 6)), [t##a##7] "v"(FLR_T(b + 7))
+        if constexpr (DM == 0x1EF) {  // D D D D L D D D D, twice: live steps S = p and S + 1
+          constexpr int S = p, N = S + 2 < CS ? S + 2 : 0;  // the differences two live steps ahead
+          if constexpr (S + 2 < CS)
+            asm volatile("s_waitcnt lgkmcnt(%[w])\n\t" FLR_FMA(ta0) FLR_FMA(ta1) FLR_FMA(ta2) FLR_FMA(ta3) FLR_FMA(d0)
+                             FLR_SUB(n0, x0, j0, L0) FLR_FMA(ta4) FLR_FMA(ta5) FLR_FMA(ta6) FLR_FMA(ta7)
+                                 FLR_FMA(tb0) FLR_FMA(tb1) FLR_FMA(tb2) FLR_FMA(tb3) FLR_FMA(d1)
+                                     FLR_SUB(d0, x1, j1, L1) FLR_FMA(tb4) FLR_FMA(tb5) FLR_FMA(tb6) FLR_FMA(tb7)
+                         : [acc] "+v"(acc), [d0] "+v"(d[S % 3]), [d1] "+v"(d[(S + 1) % 3]), [n0] "=&v"(d[(S + 2) % 3])
+                         : [x0] "v"(xv[N % 4]), [j0] "v"(v[N / 4][N % 4]), [L0] "n"(N / 4), [x1] "v"(xv[(N + 1) % 4]),
+                           [j1] "v"(v[(N + 1) / 4][(N + 1) % 4]), [L1] "n"((N + 1) / 4), [w] "n"(cnt), FLR_T8(a, 0),
+                           FLR_T8(b, 8));
+          else
+            asm volatile("s_waitcnt lgkmcnt(%[w])\n\t" FLR_FMA(ta0) FLR_FMA(ta1) FLR_FMA(ta2) FLR_FMA(ta3) FLR_FMA(d0)
+                             FLR_FMA(ta4) FLR_FMA(ta5) FLR_FMA(ta6) FLR_FMA(ta7) FLR_FMA(tb0) FLR_FMA(tb1)
+                                 FLR_FMA(tb2) FLR_FMA(tb3) FLR_FMA(d1) FLR_FMA(tb4) FLR_FMA(tb5) FLR_FMA(tb6)
+                                     FLR_FMA(tb7)
+                         : [acc] "+v"(acc)
+                         : [d0] "v"(d[S % 3]), [d1] "v"(d[(S + 1) % 3]), [w] "n"(cnt), FLR_T8(a, 0), FLR_T8(b, 8));
+        } else {  // L L D L L D D D D: live steps S .. S + 3, S = 4 p; temporaries da, db, dc = d[S % 3] ..
+          constexpr int S = 4 * p;
+          float &da = d[S % 3], &db = d[(S + 1) % 3], &dc = d[(S + 2) % 3];
+          if constexpr (S + 4 < CS)
+            asm volatile("s_waitcnt lgkmcnt(%[w])\n\t" FLR_FMA(da) FLR_SUB(dc, x2, j2, L0) FLR_FMA(db)
+                             FLR_SUB(da, x3, j3, L0) FLR_FMA(t0) FLR_FMA(dc) FLR_SUB(db, x0, j4, L1) FLR_FMA(da)
+                                 FLR_SUB(dc, x1, j5, L1) FLR_FMA(t1) FLR_FMA(t2) FLR_FMA(t3) FLR_FMA(t4)
+                         : [acc] "+v"(acc), [da] "+v"(da), [db] "+v"(db), [dc] "+v"(dc)
+                         : [x0] "v"(xv[0]), [x1] "v"(xv[1]), [x2] "v"(xv[2]), [x3] "v"(xv[3]), [j2] "v"(v[p][2]),
+                           [j3] "v"(v[p][3]), [j4] "v"(v[p + 1 < NQ ? p + 1 : p][0]),
+                           [j5] "v"(v[p + 1 < NQ ? p + 1 : p][1]), [L0] "n"(p), [L1] "n"(p + 1), [w] "n"(cnt),
+                           [t0] "v"(FLR_T(0)), [t1] "v"(FLR_T(1)), [t2] "v"(FLR_T(2)), [t3] "v"(FLR_T(3)),
+                           [t4] "v"(FLR_T(4)));
+          else  // the chunk's last period: no step past it
+            asm volatile("s_waitcnt lgkmcnt(%[w])\n\t" FLR_FMA(da) FLR_SUB(dc, x2, j2, L0) FLR_FMA(db)
+                             FLR_SUB(da, x3, j3, L0) FLR_FMA(t0) FLR_FMA(dc) FLR_FMA(da) FLR_FMA(t1) FLR_FMA(t2)
+                                 FLR_FMA(t3) FLR_FMA(t4)
+                         : [acc] "+v"(acc), [da] "+v"(da), [db] "+v"(db), [dc] "+v"(dc)
+                         : [x2] "v"(xv[2]), [x3] "v"(xv[3]), [j2] "v"(v[p][2]), [j3] "v"(v[p][3]), [L0] "n"(p),
+                           [w] "n"(cnt), [t0] "v"(FLR_T(0)), [t1] "v"(FLR_T(1)), [t2] "v"(FLR_T(2)),
+                           [t3] "v"(FLR_T(3)), [t4] "v"(FLR_T(4)));
+        }
+#undef FLR_T8
+#undef FLR_T
+        // the reads this group used up are free: the next RQ ahead into them
+        static_for(
+            [&readq](auto E) {
+              constexpr int q = done + decltype(E)::value;
+              if constexpr (4 * q + 3 < n0 + G * ND && q + RQ < NQT) readq(std::integral_constant<int, q + RQ>{});
+            },
+            std::make_integer_sequence<int, (G * ND + 3) / 4 + 1>{});
+      },
+      std::make_integer_sequence<int, Pt::PPC / G>{});
+  return acc;
+}
+#undef FLR_SUB
+#undef FLR_FMA
+
 // One segment of steps of one tile (one wave): chain c of each lane's pair; the
 // running chain sums in A[c][min(i,j)][max(i,j)] (first: start from 0).
 //
@@ -489,15 +691,36 @@ __device__ __forceinline__ void static_for(F&& f, std::integer_sequence<int, U..
 // the wave is the workgroup and reads only what it staged.
 // NST: the ring's stages (the loop's unroll); TWO: two chains per lane, pairs
 // (i, j) and (i + 4, j) of an off-diagonal tile (ref_chain2_kernel).
-template <bool DIAG, int NST = NSTAGE, bool TWO = false>
+// DM != 0: a dead region (DeadPlan, dead_chunk) with the dead-tap mask DM — Xc
+// is the live stream, `steps` its live steps, Tc chain c's dead stream, staged
+// behind each stage's J rows by NT more DMAs per chunk; a lane's pair is mixed
+// when exactly one of its rows is among the nneg negated ones.
+template <bool DIAG, int NST = NSTAGE, bool TWO = false, int DM = 0>
 __device__ __forceinline__ void ref_chain_tile(float* lds, const Tile T, const int c, const float* __restrict__ Xc,
-                                               int64_t ldc, int K, int64_t steps, int first,
-                                               float* __restrict__ A) {
+                                               int64_t ldc, int K, int64_t steps, int first, float* __restrict__ A,
+                                               const float* __restrict__ Tc = nullptr, int nneg = 0) {
   using S = Staging<DIAG>;
   static_assert(!(TWO && DIAG), "two chains per lane on off-diagonal tiles only");
   static_assert(NST % 2 == 0 && NST >= 4, "two register buffers");
+  constexpr int NT = [] {
+    if constexpr (DM != 0)
+      return DeadPat<DM>::NT;
+    else
+      return 0;
+  }();
+  constexpr int TCH = [] {
+    if constexpr (DM != 0)
+      return DeadPat<DM>::TCH;
+    else
+      return 0;
+  }();
+  static_assert(NT <= 2 && !(TWO && DM), "the dead stream's DMA statements below");
+  constexpr int STG = STAGE + NT * 256;          // floats per ring stage: the J rows, then the dead stream's chunk
+  constexpr int ZERO = NST * STG;                // (DM) the zero block the unmixed lanes read: NT KB
+  static_assert((ZERO + NT * 256) * 4 <= NSTAGE * STAGE * 4, "inside the kernel's one LDS array");
+  static_assert((NST - 1) * STG * 4 < 65536, "ds_read_b128's 16-bit offset reaches every stage");
   constexpr int NXI = TWO ? 2 : 1;               // x_i loads per body
-  constexpr int OPB = S::DPW + NXI;              // vector-memory ops per body
+  constexpr int OPB = S::DPW + NT + NXI;         // vector-memory ops per body
   static_assert((NST - 2) * OPB + NXI < 64, "vmcnt counts to 63");
   const int lane = threadIdx.x & 63, r = lane >> 4, jl = lane & 15;
   // this lane's pair (i, j) and the staged row it reads
@@ -552,6 +775,7 @@ __device__ __forceinline__ void ref_chain_tile(float* lds, const Tile T, const i
     gj = gj < K ? gj : K - 1;
     voj[u] = (uint32_t)((int64_t)(gj - jrow0) * rs * 4 + 16 * ((lane % NQ) ^ slot_swz(s)) - 1024 * (u - 2) + 2048);
   }
+  const uint32_t vot = 16 * lane;  // (DM) the dead stream's chunk: 16 B per lane
   // x_i: lane jl of DPP row r loads steps 4 jl .. 4 jl + 3 of the row's I row
   const int irow0 = min(DIAG ? SB * T.X + IW * T.g : i - r, K - 1);
   const char* sbi = reinterpret_cast<const char*>(Xc + (int64_t)irow0 * rs + (int64_t)c * ldc);
@@ -570,7 +794,7 @@ __device__ __forceinline__ void ref_chain_tile(float* lds, const Tile T, const i
     const int64_t co = (int64_t)ch * CS * 4;
     if (FLR_REF_ABL == 3) return;
     const char* sb = sbj + co;
-    const uint32_t m = (uint32_t)(uintptr_t)lds + 4 * slot * STAGE + 2048;
+    const uint32_t m = (uint32_t)(uintptr_t)lds + 4 * slot * STG + 2048;
     // M0 written in the statement that reads it; no other instruction of this
     // kernel reads M0 (the compiler emits none: checked in the ISA), so it is
     // not restored
@@ -590,6 +814,21 @@ __device__ __forceinline__ void ref_chain_tile(float* lds, const Tile T, const i
                    : "memory");
 #undef FLR_DMA
     static_assert(S::DPW == 4 || S::DPW == 5, "the DMA statements above");
+    if constexpr (NT > 0) {  // the dead stream's chunk: lane l's 16 B at byte 16 l of the stage's T area
+      const char* st = reinterpret_cast<const char*>(Tc) + (int64_t)ch * TCH * 4;
+      const uint32_t mt = (uint32_t)(uintptr_t)lds + 4 * (slot * STG + STAGE);
+      if constexpr (NT == 2)
+        asm volatile("s_mov_b32 m0, %[m]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[v], %[sb] offset:0\n\t"
+                     "global_load_lds_dwordx4 %[v], %[sb] offset:1024"
+                     :
+                     : [m] "s"(mt), [sb] "s"(st), [v] "v"(vot)
+                     : "memory");
+      else
+        asm volatile("s_mov_b32 m0, %[m]\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %[v], %[sb] offset:0"
+                     :
+                     : [m] "s"(mt), [sb] "s"(st), [v] "v"(vot)
+                     : "memory");
+    }
     asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(x) : "v"(voi), "s"(sbi + co) : "memory");
     if constexpr (TWO) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(x2) : "v"(voi2), "s"(sbi + co) : "memory");
   };
@@ -602,10 +841,24 @@ __device__ __forceinline__ void ref_chain_tile(float* lds, const Tile T, const i
 #pragma unroll
     for (int q = 0; q < NQ; ++q)
       if (FLR_REF_ABL != 2)
-        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v[q]) : "v"(a[q]), "n"(decltype(st)::value * STAGE * 4)
+        asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(v[q]) : "v"(a[q]), "n"(decltype(st)::value * STG * 4)
                      : "memory");
   };
 
+  // (DM) the dead stream's LDS address per stage: the stage's T area on a mixed
+  // lane, the zero block (zeroed here, by this wave) on the others
+  uint32_t ta[NST];
+  if constexpr (DM != 0) {
+    const bool mixed = valid && ((i < nneg) != (j < nneg));
+    static_assert(NT * 256 % 64 == 0, "the zero block in whole 16-B pieces per lane");
+#pragma unroll
+    for (int q = 0; q < NT * 256 / 256; ++q)
+      *reinterpret_cast<f32x4*>(lds + ZERO + 256 * q + 4 * lane) = f32x4{0.f, 0.f, 0.f, 0.f};
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+    for (int u = 0; u < NST; ++u)
+      ta[u] = (uint32_t)(uintptr_t)(mixed ? lds + u * STG + STAGE : lds + ZERO);
+  }
   f32x4 va[NQ], vb[NQ];
   f32x4 xs[NST], xs2[NST];
   auto body = [&](auto U, int ch, f32x4(&vc)[NQ], f32x4(&vn)[NQ]) {
@@ -621,7 +874,9 @@ __device__ __forceinline__ void ref_chain_tile(float* lds, const Tile T, const i
     if constexpr (TWO) asm volatile("" : "+v"(xs2[u]));
     issue(ch + NST - 1, (u + NST - 1) % NST, xs[(u + NST - 1) % NST], xs2[(u + NST - 1) % NST]);
     rows(std::integral_constant<int, (u + 1) % NST>{}, vn, ra);
-    if constexpr (TWO)
+    if constexpr (DM != 0)
+      acc = dead_chunk<DM>(xs[u], vc, acc, ta[u]);
+    else if constexpr (TWO)
       chain_chunk2(xs[u], xs2[u], vc, acc, acc2);
     else if (FLR_REF_ABL != 5)
       acc = chain_chunk(xs[u], vc, acc);
@@ -659,6 +914,47 @@ __global__ __launch_bounds__(64) void ref_chain_kernel(const float* __restrict__
     ref_chain_tile<true>(lds, T, c, Xc, ldc, K, steps, first, A);
   else
     ref_chain_tile<false>(lds, T, c, Xc, ldc, K, steps, first, A);
+}
+
+// A dead region (DeadPlan) of every tile: grid as ref_chain_kernel, t0 = 0.
+// A same-kind pair's dead steps are fma(+0, +0, s) = s (fl(g - g) = +0 for
+// finite g; ref_finish_kernel covers the rest), so a wave without a mixed pair
+// runs the live stream alone, through the plain tile; a wave with one runs the
+// two streams in the chain's order.  Same LDS array as ref_chain_kernel: four
+// workgroups per CU.
+template <int DM>
+__global__ __launch_bounds__(64) void ref_chain_dead_kernel(const float* __restrict__ Xl, int64_t ldc,
+                                                            const float* __restrict__ Tb, int64_t ldt, int K,
+                                                            int nneg, int64_t steps, int first,
+                                                            float* __restrict__ A) {
+  __shared__ __attribute__((aligned(16))) float lds[NSTAGE * STAGE];
+  const int c = (int)(blockIdx.x & 7);
+  const Tile T = tile_of((int)(blockIdx.x >> 3));
+  // the lane's pair, as ref_chain_tile numbers them
+  const int lane = threadIdx.x & 63, r = lane >> 4, jl = lane & 15;
+  int i, j;
+  bool keep = true;
+  if (T.diag) {
+    const int a = IW * T.g + r, o = jl + 1;
+    i = SB * T.X + a;
+    j = SB * T.X + ((a + o) & (SB - 1));
+    keep = o < SB / 2 || a < SB / 2;
+  } else {
+    i = SB * T.X + IW * T.g + r;
+    j = SB * T.Y + JW * T.h + jl;
+  }
+  const bool mixed = keep && i < K && j < K && ((i < nneg) != (j < nneg));
+  const float* Tc = Tb + (int64_t)c * ldt;
+  if (__builtin_amdgcn_ballot_w64(mixed) == 0) {
+    if (T.diag)
+      ref_chain_tile<true>(lds, T, c, Xl, ldc, K, steps, first, A);
+    else
+      ref_chain_tile<false>(lds, T, c, Xl, ldc, K, steps, first, A);
+  } else if (T.diag) {
+    ref_chain_tile<true, NSTD, false, DM>(lds, T, c, Xl, ldc, K, steps, first, A, Tc, nneg);
+  } else {
+    ref_chain_tile<false, NSTD, false, DM>(lds, T, c, Xl, ldc, K, steps, first, A, Tc, nneg);
+  }
 }
 
 // K >= 256 (more tiles than SIMDs: the chains are throughput-bound, not
@@ -1170,7 +1466,7 @@ struct TailCols {
 };
 __global__ void ref_finish_kernel(const float* __restrict__ A, int chains, const float* __restrict__ X,
                                   const TailCols tc, int K, int64_t P, int64_t ldx, int64_t R, int t0, int t1,
-                                  double* __restrict__ D) {
+                                  double* __restrict__ D, const int* __restrict__ dflag, int nneg) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= (int64_t)K * K) return;
   const int i = (int)(idx / K), j = (int)(idx % K);
@@ -1203,6 +1499,9 @@ __global__ void ref_finish_kernel(const float* __restrict__ A, int chains, const
       s = __builtin_fmaf(d, d, s);
     }
     v = (double)sqrt_rn(s);
+    // a dead region skipped this same-kind pair's dead steps: where a dead
+    // value of g is not finite they are fl(g - g) = NaN, and so is the sum
+    if (dflag && *dflag && ((i < nneg) == (j < nneg))) v = __builtin_nan("");
   }
   D[(int64_t)i * K + j] = v;
   D[(int64_t)j * K + i] = v;
@@ -1227,7 +1526,11 @@ extern "C" size_t flr_pairwise_l2_reference_workspace(int64_t K, int64_t P) {
   const int64_t per_step = (K > QJ ? quad_rows(K) : K) * 8 * 4;
   const int64_t nseg = (per_step * Rc + XC_CAP - 1) / XC_CAP;
   const int64_t Rs = ((R + nseg - 1) / nseg + XC_GROUP - 1) / XC_GROUP * XC_GROUP;
-  return n + (size_t)(per_step * Rs + XC_SLACK + (K > QJ ? quad_slack(K) : 0));
+  // dead regions (run_chains), a one-GPU mode of moderate K: the dead streams
+  // (one row: under P floats, and a few KB per block) and the padding of up
+  // to 40 regions' streams to XC_GROUP steps
+  const int64_t regions = K <= 512 ? 4 * P + (int64_t(4) << 20) + 40 * XC_GROUP * per_step : 0;
+  return n + (size_t)(per_step * Rs + XC_SLACK + (K > QJ ? quad_slack(K) : 0) + regions);
 }
 
 extern "C" int flr_pairwise_l2_reference_tiles(int64_t K) {
@@ -1271,13 +1574,68 @@ static WaveRuns wave_runs(const int64_t* taps, int64_t ntaps, int64_t r0, int64_
   return wr;
 }
 
+// The dead-tap masks with a dead region form (ref_chain_dead_kernel<DM>): C3's
+// one live tap (the centre) and its four (the 2 x 2 corner of a stride-2 block)
+constexpr int DM_ONE = 0x1EF, DM_FOUR = 0x04F;
+// A tap block that can run as a dead region: its plan, its live stream's steps
+// per chain (whole periods, DeadPlan) and its dead stream in the workspace.
+struct DeadBlock {
+  bool fast = false;
+  DeadPlan live{}, deadp{};  // the live taps' / the dead taps' nibbles
+  int dm = 0;
+  int64_t r0 = 0, S = 0;     // the block's chain steps [r0, r0 + S)
+  int64_t Ll = 0, Lp = 0;    // live steps per chain, padded to XC_GROUP
+  int64_t ldt = 0, toff = 0; // dead stream: floats per chain, offset of chain 0
+};
+static DeadBlock dead_block(int64_t off, int64_t co, int64_t ci, int64_t kk, uint64_t dm) {
+  DeadBlock b;
+  const int m = (int)(dm & 0x1ff);
+  if (kk != 9 || (m != DM_ONE && m != DM_FOUR) || off % 8 != 0 || (co * ci * 9) % 8 != 0) return b;
+  b.fast = true;
+  b.dm = m;
+  b.live.on = b.deadp.on = 1;
+  for (int w = 0; w < 9; ++w) {  // a period's taps in the chain's order
+    const int t = 8 - w;
+    DeadPlan& p = ((m >> t) & 1) ? b.deadp : b.live;
+    const int n = ((m >> t) & 1) ? b.deadp.nd++ : b.live.nl++;
+    p.tap |= (uint64_t)t << (4 * n);
+    p.rank |= (uint64_t)n << (4 * t);
+  }
+  b.live.nd = b.deadp.nd;
+  b.deadp.nl = b.live.nl;
+  b.r0 = off / 8;
+  b.S = co * ci * 9 / 8;
+  const int64_t np = (b.S + 16) / 9;  // periods of virtual steps 0 .. S + 7
+  b.Ll = np * b.live.nl;
+  b.Lp = (b.Ll + XC_GROUP - 1) / XC_GROUP * XC_GROUP;
+  // the mixed waves run NSTD chunks per trip, CS / nl periods per chunk, and
+  // prefetch NSTD - 1 chunks (1 KB per DMA) past the last
+  const int64_t tch = CS / b.live.nl * b.deadp.nd, trip = (int64_t)NSTD * CS;
+  b.ldt = ((b.Ll + trip - 1) / trip * NSTD + NSTD) * tch + 512;
+  b.ldt = (b.ldt + 63) / 64 * 64;
+  return b;
+}
+// One chain launch of a segment: a stretch of plain steps, or a dead region
+struct Region {
+  int64_t a, b;  // chain steps [a, b)
+  int blk;       // the dead region's block, or -1
+  int64_t pos;   // its streams' first step in the segment's workspace
+};
+
 // The chains of tiles [t0, t1) over `steps` chain steps of X (coordinates
 // 0 .. 8 steps - 1 of each row), continuing the sums in A (first: from 0):
 // per segment the chain-major transpose (skipping the tap-major blocks), the
 // tap blocks' rewrite, the chain kernel.
+// With dead taps (every tile in one call, FLR_REF_DEAD_SKIP not 0) a segment is
+// split into regions, each its own chain launch continuing A: a 3 x 3 block
+// with a mask of DM_ONE / DM_FOUR that lies whole inside the segment at
+// off % 8 == 0 is a dead region (its live taps rewritten compactly, its dead
+// ones read from the shared dead stream), the stretches between them run as
+// before.  Any other block is expanded from gdead as before: the same bits.
+// *dflag: the device flag "a dead value of g is not finite", when a region ran.
 static int run_chains(const float* X, int64_t K, int64_t steps_total, int64_t ldx, const int64_t* taps, int64_t ntaps,
                       const uint64_t* dead, const float* gdead, int64_t nneg, int first, float* A, void* ws,
-                      size_t ws_bytes, int t0, int t1, hipStream_t st) {
+                      size_t ws_bytes, int t0, int t1, hipStream_t st, const int** dflag) {
   const size_t na = a_bytes(K);
   if (ws_bytes < na) return FLR_ERR_WORKSPACE;
   const int64_t R = steps_total;
@@ -1322,48 +1680,142 @@ static int run_chains(const float* X, int64_t K, int64_t steps_total, int64_t ld
     return FLR_OK;
   }
   const int64_t per_step = K * 8 * 4;
-  const int64_t ldc = (int64_t)((ws_bytes - na - XC_SLACK) / (size_t)per_step) / XC_GROUP * XC_GROUP;
+  const bool all_tiles = t0 == 0 && t1 == ntiles_of((int)K);
+  const int nn = (int)std::min<int64_t>(nneg, K);
+  // the blocks that may run as dead regions, and their dead streams at the
+  // workspace's end (then a flag word)
+  std::vector<DeadBlock> db((size_t)ntaps);
+  size_t tfloats = 0;
+  const char* skip_knob = flr::knob("FLR_REF_DEAD_SKIP");
+  if (dead && gdead && all_tiles && !use_two_chains(K) && !(skip_knob && skip_knob[0] == '0'))
+    for (int64_t b = 0; b < ntaps; ++b) {
+      db[(size_t)b] = dead_block(taps[4 * b], taps[4 * b + 1], taps[4 * b + 2], taps[4 * b + 3], dead[b]);
+      if (!db[(size_t)b].fast) continue;
+      db[(size_t)b].toff = (int64_t)tfloats;
+      tfloats += (size_t)(8 * db[(size_t)b].ldt);
+    }
+  size_t xc_end = ws_bytes;  // the chain-major streams end here
+  if (tfloats > 0) {
+    const size_t tb = tfloats * 4 + 256;
+    if (ws_bytes >= na + (size_t)XC_SLACK + (size_t)(per_step * XC_GROUP) + tb + 256)
+      xc_end = (ws_bytes - tb) / 256 * 256;
+    else  // no room for the dead streams: every block expanded
+      for (auto& b : db) b.fast = false;
+  }
+  float* Tall = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + xc_end);
+  int* flag = reinterpret_cast<int*>(Tall + tfloats);
+  const int64_t ldc = (int64_t)((xc_end - na - XC_SLACK) / (size_t)per_step) / XC_GROUP * XC_GROUP;
   if (ldc < XC_GROUP) return FLR_ERR_WORKSPACE;
-  const int64_t nseg = (R + ldc - 1) / ldc;
-  const int64_t Rs = ((R + nseg - 1) / nseg + XC_GROUP - 1) / XC_GROUP * XC_GROUP;  // <= ldc
-  float* Xc = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + na);
+  // a segment's regions, their streams packed at multiples of XC_GROUP steps;
+  // returns the steps of workspace they take
+  auto plan = [&](int64_t r0, int64_t steps, bool regions, std::vector<Region>& out) {
+    out.clear();
+    int64_t cur = r0, pos = 0;
+    auto live = [&](int64_t a, int64_t b) {
+      out.push_back({a, b, -1, pos});
+      pos += (b - a + XC_GROUP - 1) / XC_GROUP * XC_GROUP;
+    };
+    for (int64_t b = 0; regions && b < ntaps; ++b) {
+      const DeadBlock& d = db[(size_t)b];
+      if (!d.fast || d.r0 < cur || d.r0 + d.S > r0 + steps) continue;
+      if (d.r0 > cur) live(cur, d.r0);
+      out.push_back({d.r0, d.r0 + d.S, (int)b, pos});
+      pos += d.Lp;
+      cur = d.r0 + d.S;
+    }
+    if (cur < r0 + steps) live(cur, r0 + steps);
+    return pos;
+  };
+  std::vector<Region> regs;
+  // one segment when the regions of the whole chain fit (the dead regions are
+  // shorter than their blocks), else segments of equal steps as before
+  int64_t nseg = (R + ldc - 1) / ldc;
+  if (tfloats > 0 && plan(0, R, true, regs) <= ldc) nseg = 1;
+  const int64_t Rs = nseg == 1 ? R : ((R + nseg - 1) / nseg + XC_GROUP - 1) / XC_GROUP * XC_GROUP;  // <= ldc
+  float* Xc0 = reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + na);
+  bool streams_made = false, started = false;
   for (int64_t seg = 0; seg < nseg; ++seg) {
-    const int64_t r0 = seg * Rs, steps = (R - r0 < Rs) ? R - r0 : Rs;
-    if (steps <= 0) break;
-    const WaveRuns runs = wave_runs(taps, ntaps, r0, steps);
-    int rc = FLR_OK;
-    if (runs.pre[runs.n] > 0) {
-      hipLaunchKernelGGL(chain_transpose_kernel, dim3((unsigned)((runs.pre[runs.n] + 3) / 4), (unsigned)K), dim3(256),
-                         0, st, X, ldx, r0, steps, ldc, Xc, runs);
-      if ((rc = launch_status("chain_transpose_kernel")) != FLR_OK) return rc;
+    const int64_t sr0 = seg * Rs, ssteps = (R - sr0 < Rs) ? R - sr0 : Rs;
+    if (ssteps <= 0) break;
+    if (plan(sr0, ssteps, tfloats > 0, regs) > ldc) plan(sr0, ssteps, false, regs);  // (the padding of many regions)
+    for (const Region& rg : regs) {
+      const int fst = (first && !started) ? 1 : 0;
+      started = true;
+      float* Xc = Xc0 + rg.pos;
+      int rc = FLR_OK;
+      if (rg.blk >= 0) {  // a dead region
+        const DeadBlock& d = db[(size_t)rg.blk];
+        const int64_t off = taps[4 * rg.blk], co = taps[4 * rg.blk + 1], ci = taps[4 * rg.blk + 2];
+        if (!streams_made) {  // every block's dead stream, once per call
+          streams_made = true;
+          if (hipMemsetAsync(Tall, 0, tfloats * 4 + 4, st) != hipSuccess) return FLR_ERR_HIP;
+          for (int64_t b = 0; b < ntaps; ++b) {
+            const DeadBlock& e = db[(size_t)b];
+            if (!e.fast) continue;
+            const int64_t n = taps[4 * b + 1] * taps[4 * b + 2] * e.deadp.nd;
+            hipLaunchKernelGGL(dead_stream_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, gdead,
+                               taps[4 * b], (int)taps[4 * b + 1], (int)taps[4 * b + 2], e.deadp, e.ldt, Tall + e.toff,
+                               flag);
+            if ((rc = launch_status("dead_stream_kernel")) != FLR_OK) return rc;
+          }
+          if (dflag) *dflag = flag;
+        }
+        // the live stream's slots no step fills: the first period and, from the
+        // shortest chain's last period on, the rest of the padded stream
+        const int64_t zs = d.S / 9 * d.live.nl;
+        hipLaunchKernelGGL(zero_slots_kernel, dim3((unsigned)(K * 8)), dim3(256), 0, st, Xc, ldc, d.live.nl, zs, d.Lp);
+        if ((rc = launch_status("zero_slots_kernel")) != FLR_OK) return rc;
+        const int64_t cit = TAP_ROWS / d.live.nl;  // input channels per tile
+        const int64_t tiles = (co + TAP_CO - 1) / TAP_CO * ((ci + cit - 1) / cit);
+        const bool vec = off % 4 == 0 && co % TAP_CO == 0;
+        auto kern = vec ? tap_chain_kernel<9, true, true> : tap_chain_kernel<9, false, true>;
+        hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)K), dim3(256), 0, st, X, ldx, off, (int)co, (int)ci, 9,
+                           d.r0, d.S, ldc, Xc, (const float*)nullptr, (uint64_t)d.dm, nn, d.live);
+        if ((rc = launch_status("tap_chain_kernel")) != FLR_OK) return rc;
+        if (d.dm == DM_ONE)
+          hipLaunchKernelGGL(ref_chain_dead_kernel<DM_ONE>, dim3(8 * (t1 - t0)), dim3(64), 0, st, Xc, ldc,
+                             Tall + d.toff, d.ldt, (int)K, nn, d.Ll, fst, A);
+        else
+          hipLaunchKernelGGL(ref_chain_dead_kernel<DM_FOUR>, dim3(8 * (t1 - t0)), dim3(64), 0, st, Xc, ldc,
+                             Tall + d.toff, d.ldt, (int)K, nn, d.Ll, fst, A);
+        if ((rc = launch_status("ref_chain_dead_kernel")) != FLR_OK) return rc;
+        continue;
+      }
+      const int64_t r0 = rg.a, steps = rg.b - rg.a;
+      const WaveRuns runs = wave_runs(taps, ntaps, r0, steps);
+      if (runs.pre[runs.n] > 0) {
+        hipLaunchKernelGGL(chain_transpose_kernel, dim3((unsigned)((runs.pre[runs.n] + 3) / 4), (unsigned)K), dim3(256),
+                           0, st, X, ldx, r0, steps, ldc, Xc, runs);
+        if ((rc = launch_status("chain_transpose_kernel")) != FLR_OK) return rc;
+      }
+      for (int64_t b = 0; b < ntaps; ++b) {  // the tap-major blocks of this segment, rewritten
+        const int64_t off = taps[4 * b], co = taps[4 * b + 1], ci = taps[4 * b + 2], kk = taps[4 * b + 3];
+        if (off + co * ci * kk <= 8 * r0 || off >= 8 * (r0 + steps)) continue;
+        const int64_t tiles = (co + TAP_CO - 1) / TAP_CO * ((ci + TAP_ROWS / kk - 1) / (TAP_ROWS / kk));
+        const bool vec = off % 4 == 0 && co % TAP_CO == 0;  // 16-B aligned rows, full 32-channel tiles
+        auto kern = kk == 9 ? (vec ? tap_chain_kernel<9, true> : tap_chain_kernel<9, false>)
+                  : kk == 1 ? (vec ? tap_chain_kernel<1, true> : tap_chain_kernel<1, false>)
+                            : (vec ? tap_chain_kernel<0, true> : tap_chain_kernel<0, false>);
+        const uint64_t dm = dead ? dead[b] : 0;
+        hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)K), dim3(256), 0, st, X, ldx, off, (int)co, (int)ci,
+                           (int)kk, r0, steps, ldc, Xc, dm ? gdead : nullptr, dm, nn, DeadPlan{});
+        if ((rc = launch_status("tap_chain_kernel")) != FLR_OK) return rc;
+      }
+      const int64_t padded = (steps + XC_GROUP - 1) / XC_GROUP * XC_GROUP;  // <= Rs <= ldc
+      if (padded > steps) {
+        hipLaunchKernelGGL(zero_slots_kernel, dim3((unsigned)(K * 8)), dim3(256), 0, st, Xc, ldc, 0, steps, padded);
+        if ((rc = launch_status("zero_slots_kernel")) != FLR_OK) return rc;
+      }
+      if (all_tiles && use_two_chains(K)) {  // every pair: the two-chain tiles
+        hipLaunchKernelGGL(ref_chain2_kernel, dim3(8 * ntiles2_of((int)K)), dim3(64), 0, st, Xc, ldc, (int)K, steps,
+                           fst, A);
+        rc = launch_status("ref_chain2_kernel");
+      } else {
+        hipLaunchKernelGGL(ref_chain_kernel, dim3(8 * (t1 - t0)), dim3(64), 0, st, Xc, ldc, (int)K, steps, t0, fst, A);
+        rc = launch_status("ref_chain_kernel");
+      }
+      if (rc != FLR_OK) return rc;
     }
-    for (int64_t b = 0; b < ntaps; ++b) {  // the tap-major blocks of this segment, rewritten
-      const int64_t off = taps[4 * b], co = taps[4 * b + 1], ci = taps[4 * b + 2], kk = taps[4 * b + 3];
-      if (off + co * ci * kk <= 8 * r0 || off >= 8 * (r0 + steps)) continue;
-      const int64_t tiles = (co + TAP_CO - 1) / TAP_CO * ((ci + TAP_ROWS / kk - 1) / (TAP_ROWS / kk));
-      const bool vec = off % 4 == 0 && co % TAP_CO == 0;  // 16-B aligned rows, full 32-channel tiles
-      auto kern = kk == 9 ? (vec ? tap_chain_kernel<9, true> : tap_chain_kernel<9, false>)
-                : kk == 1 ? (vec ? tap_chain_kernel<1, true> : tap_chain_kernel<1, false>)
-                          : (vec ? tap_chain_kernel<0, true> : tap_chain_kernel<0, false>);
-      const uint64_t dm = dead ? dead[b] : 0;
-      hipLaunchKernelGGL(kern, dim3((unsigned)tiles, (unsigned)K), dim3(256), 0, st, X, ldx, off, (int)co, (int)ci,
-                         (int)kk, r0, steps, ldc, Xc, dm ? gdead : nullptr, dm, (int)std::min<int64_t>(nneg, K));
-      if ((rc = launch_status("tap_chain_kernel")) != FLR_OK) return rc;
-    }
-    const int64_t padded = (steps + XC_GROUP - 1) / XC_GROUP * XC_GROUP;  // <= Rs <= ldc
-    if (padded > steps &&
-        hipMemset2DAsync(Xc + steps, (size_t)ldc * 4, 0, (size_t)(padded - steps) * 4, (size_t)(K * 8), st) != hipSuccess)
-      return FLR_ERR_HIP;
-    if (t0 == 0 && t1 == ntiles_of((int)K) && use_two_chains(K)) {  // every pair: the two-chain tiles
-      hipLaunchKernelGGL(ref_chain2_kernel, dim3(8 * ntiles2_of((int)K)), dim3(64), 0, st, Xc, ldc, (int)K, steps,
-                         (first && seg == 0) ? 1 : 0, A);
-      rc = launch_status("ref_chain2_kernel");
-    } else {
-      hipLaunchKernelGGL(ref_chain_kernel, dim3(8 * (t1 - t0)), dim3(64), 0, st, Xc, ldc, (int)K, steps, t0,
-                         (first && seg == 0) ? 1 : 0, A);
-      rc = launch_status("ref_chain_kernel");
-    }
-    if (rc != FLR_OK) return rc;
   }
   return FLR_OK;
 }
@@ -1404,9 +1856,10 @@ extern "C" int flr_pairwise_l2_reference_tap_dead(const float* X, int64_t K, int
   const int ntiles = K > 1 ? ntiles_of((int)K) : 0;
   const int t0 = (int)(part * ntiles / nparts), t1 = (int)((part + 1) * ntiles / nparts);
   float* A = reinterpret_cast<float*>(ws);
+  const int* dflag = nullptr;  // set by a dead region's plan (run_chains)
   if (K > 1 && R > 0 && t1 > t0 &&
       (rc = run_chains(X, K, R, ldx, taps, ntaps, any_dead ? dead : nullptr, gdead, nneg, 1, A, ws, ws_bytes, t0, t1,
-                       st)) != FLR_OK)
+                       st, &dflag)) != FLR_OK)
     return rc;
   // the tail coordinates' columns (identity outside the tap-major blocks)
   TailCols tc;
@@ -1430,7 +1883,7 @@ extern "C" int flr_pairwise_l2_reference_tap_dead(const float* X, int64_t K, int
     }
   const int64_t kk = K * K;
   hipLaunchKernelGGL(ref_finish_kernel, dim3((unsigned)((kk + 255) / 256)), dim3(256), 0, st, A, R > 0 ? 1 : 0, X, tc,
-                     (int)K, P, ldx, R, t0, t1, D);
+                     (int)K, P, ldx, R, t0, t1, D, dflag, (int)std::min<int64_t>(nneg, K));
   return launch_status("ref_finish_kernel");
 }
 
@@ -1471,7 +1924,7 @@ extern "C" int flr_pairwise_l2_reference_partial_tap(const float* X, int64_t K, 
     return FLR_OK;
   }
   return run_chains(X, K, steps, ldx, taps, ntaps, nullptr, nullptr, 0, first, A, ws, ws_bytes, 0, ntiles_of((int)K),
-                    st);
+                    st, nullptr);
 }
 
 extern "C" int flr_pairwise_l2_reference_partial(const float* X, int64_t K, int64_t steps, int64_t ldx, int first,
@@ -1490,6 +1943,6 @@ extern "C" int flr_pairwise_l2_reference_finish(const float* Xtail, int64_t K, i
   const int64_t kk = K * K;
   hipLaunchKernelGGL(ref_finish_kernel, dim3((unsigned)((kk + 255) / 256)), dim3(256), 0, as_stream(stream),
                      reinterpret_cast<const float*>(ws), chains ? 1 : 0, Xtail, tc, (int)K, ntail, ldx, (int64_t)0, 0,
-                     K > 1 ? ntiles_of((int)K) : 0, D);
+                     K > 1 ? ntiles_of((int)K) : 0, D, nullptr, 0);
   return launch_status("ref_finish_kernel");
 }
