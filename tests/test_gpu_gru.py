@@ -15,6 +15,9 @@ SHAPES = [  # (K, B, T, H)
     (4, 32, 16, 256),  # the model's text branch, 4 clients
     (2, 32, 4, 300),   # H not a multiple of the fused kernels' 32-unit blocks
     (2, 33, 3, 40),    # B > 32: the batched-GEMM + gate-kernel path
+    (1, 1, 2, 1),      # everything degenerate: one lane of one tile live
+    (3, 17, 3, 37),    # scalar-load path, B crosses 16, ragged unit block
+    (8, 4, 2, 96),     # 24 workgroups: the XCD remap on, 3 unit blocks per client
 ]
 
 
