@@ -627,6 +627,16 @@ int flr_conv2d_bwd_data_t_ex(const float* dy, const float* w_t, int64_t w_stride
                              int64_t H, int64_t W, int64_t Cout, int64_t KH, int64_t KW,
                              int64_t stride, int64_t pad, void* workspace,
                              size_t workspace_bytes, void* stream);
+/* 1 when flr_conv2d_fwd_t_ex (dgrad == 0) or flr_conv2d_bwd_data_t_ex (dgrad != 0)
+ * runs this geometry on the resident-B kernel: the tile's activation operand split
+ * into bf16 term images once and kept in LDS across the kernel taps, only the
+ * weights staged per K-tile.  Taken for stride-1 "same" convolutions with 64
+ * channels on both sides whose H*W divides 128 and whose default split-K count is
+ * 1 (ResNet-18's layer1); the bits are the default kernel's.  The knob
+ * FLR_CONV_RESIDENT=0 (flr_set_knob, read per launch) turns the form off: 0 then. */
+int flr_conv2d_resident_ok(int64_t K, int64_t B, int64_t Cin, int64_t H, int64_t W,
+                           int64_t Cout, int64_t KH, int64_t KW, int64_t stride,
+                           int64_t pad, int dgrad);
 /* zero_dead_taps: write the dead taps' slabs of dw_t as zeros (1) or leave
  * them untouched (0: the caller never reads them, see
  * flr_clip_sgd_step_blocked). */

@@ -1,7 +1,8 @@
 // The tiled GEMM kernels behind every tap-major convolution, the im2col / stem
 // GEMMs and the batched GEMM: the shared epilogue, tgemm_kernel (fp32 LDS
 // images: exact f32 and the pipelined bf16x6 loop), sgemm_kernel (split at
-// stash), wsgemm_kernel (transposed images: the weight gradient),
+// stash), rgemm_kernel (the activation tile resident in LDS across the taps:
+// layer1), wsgemm_kernel (transposed images: the weight gradient),
 // treduce_kernel (split-K), then the tile / split-K policy and launch().
 #pragma once
 
@@ -575,6 +576,156 @@ __global__ __launch_bounds__(THREADS, SG_OCC) void sgemm_kernel(const Plan pl, i
   sgemm_body<Plan, MS, NS, ABL, NAR>(pl, S, part, remap);
 }
 
+// ---- the resident-B form (layer1's forward and stride-1 data gradient) ----------
+// A stride-1 "same" convolution reads the SAME reduction channels x pixels at every
+// tap, only shifted by (dh, dw): sgemm_body gathers, splits and stashes that operand
+// once per tap.  Here the workgroup tile is 64 (M) x 128 (N) with the 128 columns
+// whole images (128 / (H W) of them) and the reduction channels are 64, so the raw B
+// operand of the tile — 64 channels x 128 pixels — is split once, in the prologue,
+// into bf16 term images that stay in LDS: one per 32-channel chunk and term,
+// [129 rows][32 k] with zimg's swizzle, row = pixel index in the tile, row 128 zeros
+// (columns past N are zero rows too).  Per K-tile only the 64 x 32 weight sub-tile
+// goes through load -> split -> stash; the B fragment of lane column n at the
+// K-tile's tap is one ds_read_b128 per term at the row of the shifted pixel of the
+// same image, or row 128 where the tap reads padding (load_b8's predicate, once per
+// tap).  K-tile order, k-steps and the six products per accumulator are
+// sgemm_body's, a padding position contributes the same zero operand: bit-identical.
+// Split-K 1 only (resident_ok).  LDS: 12,288 B (A) + 49,536 B (B) = 61,824 B, two
+// workgroups per CU.
+constexpr int RES_N = 128;                 // columns of the tile: whole images
+constexpr int RES_IMG = (RES_N + 1) * SB;  // bf16 per resident term image (row 128: zeros)
+
+template <class Plan>
+__global__ __launch_bounds__(THREADS, SG_OCC) void rgemm_kernel(const Plan pl, int remap) {
+  __shared__ __attribute__((aligned(16))) __bf16 La[3][TERM_B];
+  __shared__ __attribute__((aligned(16))) __bf16 Lb[2][3][RES_IMG];
+  int bx = (int)blockIdx.x, by = (int)blockIdx.y, bz = (int)blockIdx.z;
+  if (remap & 1) xcd_tile(bx, by, bz);
+  if (remap >> 8) odd_slot_controls(remap);
+  const int k = bz;
+  const int M = pl.M(), N = pl.N(), R = pl.R();
+  const int m0 = by * BM, n0 = bx * RES_N;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int h = lane >> 5, l32 = lane & 31;
+  const int srowA = stash_row<Plan::QUAD_A>(tid), skA = stash_k<Plan::QUAD_A>(tid);
+  const int Hh = pl.g.H, Ww = pl.g.W;
+
+  const typename Plan::State8 sa = pl.init8(k, m0, n0, tid);
+  float ra[8];
+  bf16x8 pa[3];
+  f32x16 acc[1][2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[0][j][e] = 0.f;
+  auto write_a = [&]() {
+#pragma unroll
+    for (int t = 0; t < 3; ++t) *reinterpret_cast<bf16x8*>(&La[t][zimg(srowA, skA >> 3)]) = pa[t];
+  };
+  const int rlast = R - BK;  // R = taps x 64: at least two K-tiles
+  pl.load_a8(sa, 0, ra);
+  {  // the resident image: thread (pixel row 64 j + tid % 64, channels 32 c + 8 (tid / 64) .. +7)
+    const rsrc_t rb = pl.res_rsrc(k);
+    const int cs = pl.res_cs(), kc = tid >> 6;
+    float rbv[2][2][8];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int n = n0 + 64 * j + (tid & 63);
+      int oh, ow;
+      const int off = pl.res_col(n, oh, ow);
+      const unsigned vb = n < N ? (unsigned)((off + 8 * kc * cs) * 4) : SENT;
+#pragma unroll
+      for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) rbv[j][c][e] = ld1(rb, vb, (32 * c + e) * cs * 4);
+    }
+    split3(ra, pa[0], pa[1], pa[2]);
+    write_a();
+    pl.load_a8(sa, std::min(BK, rlast), ra);
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        bf16x8 pb[3];
+        split3(rbv[j][c], pb[0], pb[1], pb[2]);
+#pragma unroll
+        for (int t = 0; t < 3; ++t)
+          *reinterpret_cast<bf16x8*>(&Lb[c][t][zimg(64 * j + (tid & 63), kc)]) = pb[t];
+      }
+    if (tid < 24) {  // the zero row of the six images: four 16-B chunks each
+      bf16x8 z;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) z[q] = (__bf16)0.f;
+      *reinterpret_cast<bf16x8*>(&Lb[0][0][0] + (tid >> 2) * RES_IMG + RES_N * SB + 8 * (tid & 3)) = z;
+    }
+  }
+  // this lane's two columns: tile row and pixel
+  int crow[2], coh[2], cow[2], brow[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    crow[j] = BN * j + 32 * wn + l32;
+    pl.res_col(n0 + crow[j], coh[j], cow[j]);
+  }
+  __syncthreads();
+  // one K-tile (channel chunk C of the tap whose rows are brow): both k-steps'
+  // fragments before the first MFMA, the split of the next A sub-tile between the
+  // MFMAs, its stash, then the global loads of the one after (clamped: duplicates)
+  auto tile_body = [&](int t, auto C) {
+    constexpr int c = decltype(C)::value;
+    constexpr int NKS = BK / 16;
+    bf16x8 fa[NKS][1][3], fb[NKS][2][3];
+#pragma unroll
+    for (int s = 0; s < NKS; ++s) {
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+        fa[s][0][q] = *reinterpret_cast<const bf16x8*>(&La[q][zimg(32 * wm + l32, 2 * s + h)]);
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int q = 0; q < 3; ++q)
+          fb[s][j][q] = *reinterpret_cast<const bf16x8*>(&Lb[c][q][zimg(brow[j], 2 * s + h)]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+#define FLR_SX(TA, TB)                              \
+  _Pragma("unroll") for (int j = 0; j < 2; ++j) \
+    acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][0][TA], fb[s][j][TB], acc[0][j], 0, 0, 0);
+#pragma unroll
+    for (int s = 0; s < NKS; ++s) {
+      // product-major, small terms first (term 0 = hi, 1 = mid, 2 = lo)
+      FLR_SX(1, 1) FLR_SX(0, 2) FLR_SX(2, 0) FLR_SX(0, 1) FLR_SX(1, 0) FLR_SX(0, 0)
+    }
+#undef FLR_SX
+    split3(ra, pa[0], pa[1], pa[2]);
+    __syncthreads();  // every wave's fragment reads of tile t are done
+    write_a();
+    pl.load_a8(sa, std::min((t + 2) * BK, rlast), ra);
+    __syncthreads();
+  };
+  const int nslot = R / (2 * BK);
+  for (int slot = 0; slot < nslot; ++slot) {
+    int dh, dw;
+    pl.res_shift(slot, dh, dw);
+    dh = uni(dh);
+    dw = uni(dw);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int ih = coh[j] + dh, iw = cow[j] + dw;
+      const bool ok = (ih >= 0) & (ih < Hh) & (iw >= 0) & (iw < Ww);
+      brow[j] = ok ? crow[j] + dh * Ww + dw : RES_N;
+    }
+    tile_body(2 * slot, std::integral_constant<int, 0>());
+    tile_body(2 * slot + 1, std::integral_constant<int, 1>());
+  }
+  TileOffs<1, 2> off;
+  off.m[0] = 32 * wm;
+#pragma unroll
+  for (int j = 0; j < 2; ++j) off.n[j] = BN * j + 32 * wn;
+  off.wr = off.wc = 0;
+  store_tiles<Plan, 1, 2>(pl, 1, nullptr, k, 0, m0, n0, h, l32, M, N, acc, off);
+}
+
 // ---- the weight gradient on split-at-stash images, transposed ----------------
 // Both operands of dW are contiguous along the reduction (pixels), so the loads
 // put a half-wave on 32 consecutive pixels of one channel (coalesced) and each
@@ -1085,9 +1236,43 @@ bool fill_tile(const Plan& pl, int tile) {
   }
 }
 
+// The resident-B form (rgemm_kernel) for the forward and the stride-1 data gradient of
+// a "same" convolution with 64 output rows and 64 reduction channels whose images
+// tile 128 columns (layer1 of ResNet-18), where the default tile's split-K count is
+// 1 — the bits are the default path's.  FLR_CONV_RESIDENT=0: off (A/B, read per launch).
+inline bool conv_resident() {
+  const char* e = flr::knob("FLR_CONV_RESIDENT");
+  return !(e && e[0] == '0');
+}
+template <class Plan>
+bool resident_ok(const Plan& pl) {
+  if constexpr (!(std::is_same<Plan, FwdT>::value || std::is_same<Plan, DgradT>::value)) {
+    return false;
+  } else {
+    const Geom& g = pl.g;
+    if (!conv_resident() || gemm_form() != 5) return false;
+    if (g.stride != 1 || g.Ho != g.H || g.Wo != g.W) return false;
+    if (pl.M() != BM || pl.Cr() != 2 * BK) return false;
+    const int hw = g.H * g.W;
+    if (hw > RES_N || RES_N % hw != 0) return false;
+    if (pl.R() < 2 * pl.Cr()) return false;  // one tap: nothing is staged twice
+    const int tile = plan_tile(pl);
+    return choose_splits(pl.M(), pl.N(), pl.R(), g.Kc, (tile / 10) * (tile % 10), plan_min_kt(pl)) == 1;
+  }
+}
+template <class Plan>
+int launch_resident(const Plan& pl, hipStream_t st, const char* name) {
+  const dim3 grid((unsigned)cdiv(pl.N(), RES_N), 1u, (unsigned)pl.g.Kc);
+  hipLaunchKernelGGL((rgemm_kernel<Plan>), grid, dim3(THREADS), 0, st, pl, xcd_remap());
+  return launch_status(name);
+}
+
 template <class Plan>
 int launch(const Plan& pl, void* ws, size_t ws_bytes, hipStream_t st, const char* name) {
   if (pl.R() == 0 && !std::is_same<Plan, DgradT>::value) return FLR_OK;  // a dgrad class with no tap stores zeros
+  if constexpr (std::is_same<Plan, FwdT>::value || std::is_same<Plan, DgradT>::value) {
+    if (resident_ok(pl)) return launch_resident(pl, st, name);
+  }
   if constexpr (std::is_same<Plan, FwdT>::value || std::is_same<Plan, DgradT>::value) {
     if (pl.N() <= 32 && pl.M() % (2 * BM) == 0 && pl.R() > 0 && gemm_form() == 5 && conv_narrow()) {
       // a narrow launch under one wave of the chip (few clients per GPU): the 64 x 64

@@ -125,6 +125,26 @@ struct FwdT {  // y = conv(x, W_t): M = Cout, N = B*Ho*Wo, R = ntaps*Cin
 #pragma unroll
     for (int e = 0; e < 8; ++e) b[e] = ld1(s.rb, vb, cb + e * HW * 4);
   }
+  // ---- the resident-B form (rgemm_kernel: stride 1, Ho == H, Wo == W): the B operand
+  // of a column at no tap shift (load_b8's address at the centre tap, channel 0: float
+  // offset in the client's x; (oh, ow) its pixel), the channel stride, and a reduction
+  // slot's shift of that pixel
+  __host__ __device__ __forceinline__ int Cr() const { return g.Cin; }  // reduction channels per tap
+  __device__ __forceinline__ rsrc_t res_rsrc(int k) const { return make_rsrc(x + k * g.sxk, g.xext); }
+  __device__ __forceinline__ int res_cs() const { return (int)g.sxc; }
+  __device__ __forceinline__ int res_col(int n, int& oh, int& ow) const {
+    const uint32_t bb = udiv(n, g.d_howo), p = n - bb * g.Ho * g.Wo;
+    const uint32_t h = udiv(p, g.d_wo);
+    oh = (int)h;
+    ow = (int)(p - h * g.Wo);
+    return (int)(bb * g.sxb) + oh * g.W + ow;
+  }
+  __device__ __forceinline__ void res_shift(int slot, int& dh, int& dw) const {
+    int kh, kw;
+    slot_tap(g, slot, kh, kw);
+    dh = kh - g.pad;
+    dw = kw - g.pad;
+  }
 };
 
 // dx = conv^T(dy, W_t) over ONE stride-parity class of input pixels:
@@ -269,6 +289,24 @@ struct DgradT {
     const int cb0 = co0 * cs * 4;
 #pragma unroll
     for (int e = 0; e < 8; ++e) b[e] = ld1(s.rb, vb, cb0 + e * cs * 4);
+  }
+  // ---- the resident-B form (rgemm_kernel; stride 1, the one class, Ho == H, Wo == W):
+  // as FwdT's hooks, on dy — a slot reads output pixel (ih + pad - kh, iw + pad - kw)
+  __host__ __device__ __forceinline__ int Cr() const { return g.Cout; }
+  __device__ __forceinline__ rsrc_t res_rsrc(int k) const { return make_rsrc(dy + k * g.syk, g.yext); }
+  __device__ __forceinline__ int res_cs() const { return (int)g.syc; }
+  __device__ __forceinline__ int res_col(int n, int& oh, int& ow) const {
+    const uint32_t bb = udiv(n, d_hcwc), p = n - bb * Hc * Wc;
+    const uint32_t h = udiv(p, d_wc);
+    oh = (int)h;
+    ow = (int)(p - h * Wc);
+    return (int)(bb * g.syb) + oh * g.Wo + ow;
+  }
+  __device__ __forceinline__ void res_shift(int slot, int& dh, int& dw) const {
+    int kh, kw;
+    conv::rect_tap(crect, slot, kh, kw);
+    dh = g.pad - kh;
+    dw = g.pad - kw;
   }
 };
 

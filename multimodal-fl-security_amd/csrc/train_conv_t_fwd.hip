@@ -10,6 +10,21 @@ extern "C" int flr_conv2d_fwd_t(const float* x, const float* w_t, float* y, int6
                              ws_bytes, stream);
 }
 
+extern "C" int flr_conv2d_resident_ok(int64_t K, int64_t B, int64_t Cin, int64_t H, int64_t W, int64_t Cout,
+                                      int64_t KH, int64_t KW, int64_t stride, int64_t pad, int dgrad) {
+  if (!convt::args_ok(K, B, Cin, H, W, Cout, KH, KW, stride, pad)) return 0;
+  const conv::Geom g = conv::make_geom(K, B, Cin, H, W, Cout, KH, KW, stride, pad);
+  if (!dgrad) {
+    convt::FwdT pl;
+    pl.g = g;
+    pl.x = pl.w = nullptr; pl.y = nullptr; pl.wsk = 0;
+    return convt::resident_ok(pl) ? 1 : 0;
+  }
+  convt::DgradT cls[convt::MAX_CLASSES];
+  const int nc = convt::dgrad_classes(g, cls);
+  return nc == 1 && convt::resident_ok(cls[0]) ? 1 : 0;
+}
+
 extern "C" int flr_conv2d_fwd_t_ex(const float* x, const float* w_t, int64_t w_stride, float* y, int64_t K, int64_t B,
                                    int64_t Cin, int64_t H, int64_t W, int64_t Cout, int64_t KH, int64_t KW,
                                    int64_t stride, int64_t pad, void* ws, size_t ws_bytes, void* stream) {

@@ -132,6 +132,7 @@ SIGNATURES = {
                                                                                           _c_void_p]),
     "flr_conv2d_bwd_data_t_ex": (_int, [_c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p] + [_i64] * 10 +
                                  [_c_void_p, _size_t, _c_void_p]),
+    "flr_conv2d_resident_ok": (_int, [_i64] * 10 + [_int]),
     "flr_conv2d_bwd_weight_t": (_int, [_c_void_p, _c_void_p, _c_void_p] + [_i64] * 10 + [_int, _c_void_p, _size_t,
                                                                                          _c_void_p]),
     "flr_conv2d_bwd_weight_t_sq_slots": (_i64, [_i64] * 10),
