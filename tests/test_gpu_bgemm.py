@@ -1,7 +1,12 @@
 """GPU: the batched dense GEMM (flr_bgemm, the text branch and late-fusion MLP
-products) and ClientLinear vs fp64 torch.  Covers every operand mode (RK, KR,
-scalar gather), bias / addend epilogues, split-K and ragged shapes; and that a
-client's result does not depend on how many clients share the launch."""
+products), ClientLinear and the row sums vs fp64 torch, at the shapes of the
+text branch and the head: the RK and KR operand modes and a few scalar-gather
+shapes, a bias or an addend on contiguous outputs, one split-K shape (S = 2) and
+batch invariance at an unsplit 64 x 64-tile shape.  The rest is in
+test_gpu_bgemm_paths.py: the 128 x 128 tile with ragged edges, split-K up to 16
+and its fallback, every epilogue on each of the three store routines, strided
+and aliased outputs, the trainers' operand views, the kernel forms and knobs
+bit for bit, and the row sums' summation order."""
 import pytest
 import torch
 
