@@ -254,6 +254,44 @@ def test_reference_mode_tap_blocks_segmented(cuda):
     assert np.array_equal(want, normref.distance_matrix(X.numpy()))
 
 
+def test_reference_mode_parts_sum_to_whole(cuda):
+    """Tile ranges (part / nparts, the ranks' split) on one process: K = 40 is
+    two super-blocks, 16 off-diagonal tiles and 8 + 8 diagonal ones, so a
+    three-way cut splits a Y group.  The three parts sum to the one-call D bit
+    for bit, every off-diagonal pair is non-zero in exactly one part (the rows
+    are distinct: no true distance is 0), and D is the reference's."""
+    import ctypes
+    from flr import _capi
+    K, P, blocks = 40, 4099, [(5, 64, 7, 9)]
+    X, data = _matrix(K, P, 77, cuda)
+    assert len({X[k].numpy().tobytes() for k in range(K)}) == K
+    train = data.clone()
+    for o, co, ci, kk in blocks:
+        w = data[:, o:o + co * ci * kk].reshape(K, co, ci, kk)
+        train[:, o:o + co * ci * kk] = w.permute(0, 3, 2, 1).reshape(K, -1)
+    lib = _capi.lib()
+    nbytes = int(lib.flr_pairwise_l2_reference_workspace(K, P))
+    ws = torch.empty(nbytes + 256, dtype=torch.uint8, device=cuda)
+    wp = (ws.data_ptr() + 255) // 256 * 256
+    taps = [v for b in blocks for v in b]
+    tarr = (ctypes.c_int64 * len(taps))(*taps)
+    st = torch.cuda.current_stream().cuda_stream
+
+    def call(part, nparts):
+        D = torch.full((K, K), float("nan"), dtype=torch.float64, device=cuda)
+        _capi.call("flr_pairwise_l2_reference_tap", train.data_ptr(), K, P, train.stride(0), ctypes.addressof(tarr),
+                   len(blocks), D.data_ptr(), wp, nbytes, part, nparts, st)
+        torch.cuda.synchronize()
+        return D.cpu().numpy()
+
+    whole = call(0, 1)
+    parts = [call(p, 3) for p in range(3)]
+    assert np.array_equal(parts[0] + parts[1] + parts[2], whole)
+    holders = sum((p != 0).astype(np.int64) for p in parts)
+    assert np.array_equal(holders, 1 - np.eye(K, dtype=np.int64))
+    assert np.array_equal(whole, normref.distance_matrix(X.numpy()))
+
+
 @pytest.mark.parametrize("K,blocks,masks,nneg", [
     (16, [(5, 64, 64, 9), (36_869 + 7, 64, 3, 9), (36_869 + 7 + 1728 + 3, 128, 64, 1)],
      [0b110101011, 0b000010000, 0b1], 3),
