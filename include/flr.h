@@ -659,6 +659,18 @@ int flr_conv2d_bwd_weight_t_sq(const float* x, const float* dy, float* dw_t, int
                                int64_t Cout, int64_t KH, int64_t KW, int64_t stride,
                                int64_t pad, int zero_dead_taps, double* sq, int64_t sq_ld,
                                void* workspace, size_t workspace_bytes, void* stream);
+/* 1 when flr_conv2d_bwd_weight_t[_sq] runs this geometry on the resident weight-
+ * gradient kernel: a workgroup owns three taps of one split-K part, stages x and dy
+ * once per 64-pixel chunk of whole images as transposed bf16 term images, and reads
+ * each tap's x fragment at the shifted pixel row (or a zero row for padding).  Taken
+ * for stride-1 "same" convolutions with 64 channels on both sides whose H*W divides
+ * 64 and is a multiple of 4, with a multiple of three live taps (ResNet-18's
+ * layer1); a split-K part that begins inside an image is handled.  Split count,
+ * partials, clip-norm slots and bits are the default kernel's.  The knob
+ * FLR_WGRAD_RESIDENT=0 (flr_set_knob, read per launch) turns the form off: 0 then. */
+int flr_conv2d_wgrad_resident_ok(int64_t K, int64_t B, int64_t Cin, int64_t H, int64_t W,
+                                 int64_t Cout, int64_t KH, int64_t KW, int64_t stride,
+                                 int64_t pad);
 
 /* ---- a1 / a8 / a15: round-boundary layout moves of the training state ----
  * flr_broadcast_rows: dst[k*dst_stride + i] = src[i] (load_global: every

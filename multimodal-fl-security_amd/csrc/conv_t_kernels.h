@@ -2,7 +2,8 @@
 // GEMMs and the batched GEMM: the shared epilogue, tgemm_kernel (fp32 LDS
 // images: exact f32 and the pipelined bf16x6 loop), sgemm_kernel (split at
 // stash), rgemm_kernel (the activation tile resident in LDS across the taps:
-// layer1), wsgemm_kernel (transposed images: the weight gradient),
+// layer1), wsgemm_kernel (transposed images: the weight gradient), rwgemm_kernel
+// (the weight gradient with x and dy staged once for three taps: layer1),
 // treduce_kernel (split-K), then the tile / split-K policy and launch().
 #pragma once
 
@@ -898,6 +899,222 @@ __global__ __launch_bounds__(THREADS, SG_OCC) void wsgemm_kernel(const Plan pl, 
   }
 }
 
+// ---- the resident weight gradient (layer1) ---------------------------------------
+// wsgemm_kernel runs one workgroup per (tap, split-K part): the nine workgroups of a
+// part load, split and stash the SAME dy tile, and x tiles that are the same 64
+// channels x pixels shifted by the tap's (dh, dw) inside each image.  Here a
+// workgroup owns TG taps of one part and walks the part's pixels in chunks of
+// RW_PIX = 64 (whole images: H W divides 64; two K-tiles).  Per chunk x (unshifted)
+// and dy are loaded, split and stashed once into transposed term images
+// [pixel][64 channels] (16-B chunks swizzled by tswz of the STORED pixel row; the x
+// images carry a zero row 64), and a tap's x fragment is the two transposed reads
+// whose lanes point at k-row pixel + dh W + dw of the same image, or at the zero
+// row where load_at8's predicate fails: lane 4q + p of a 16-lane group supplies
+// k-row q's address, so the shift is a per-lane choice of row.  Every lane reads
+// (EXEC all ones), every address is 8-byte aligned.  The dy fragments of a k-step
+// feed all TG taps.
+// A split-K part may begin or end in the middle of a chunk (B = 33 at 8 x 8): the
+// chunk's images are staged whole and only the part's own K-tiles are multiplied.
+// Per accumulator: K-tiles ascending, two k-steps each, wsgemm_kernel's six
+// products — bit-identical dw, partials and clip-norm slots (slot = the tap's tile).
+// Grid (1, ntaps / TG, K S).  LDS 24,960 B (x) + 24,576 B (dy) = 49,536 B: three
+// workgroups per CU, for which the kernel is held to 168 VGPRs.
+//
+// Banks: a 32-lane half of a transposed read takes four k-rows r .. r + 3; rows of one
+// parity share 32 banks, and tswz puts r and r + 2 into different halves of the 128-B
+// row only for r % 4 == 0, so a dw = +-1 tap reads 2-way conflicted.  A swizzle that
+// holds for every r (bit 1 of the row into bit 2 of the chunk XOR, four zero rows so
+// a padded lane keeps its row's low bits: no conflict in the bank model) measured
+// the same time: the conflicts are hidden.
+constexpr int RW_PIX = 64;                  // pixels per chunk
+constexpr int RW_XIMG = (RW_PIX + 1) * 64;  // bf16 per x term image (row 64: zeros)
+constexpr int RW_YIMG = RW_PIX * 64;        // bf16 per dy term image
+constexpr int RW_TG = 3;                    // taps per workgroup (one kernel row of a 3 x 3)
+
+template <class Plan, int TG>
+__global__ __launch_bounds__(THREADS, 3) void rwgemm_kernel(const Plan pl, int S, float* __restrict__ part, int remap) {
+  __shared__ __attribute__((aligned(16))) __bf16 Lx[3][RW_XIMG];
+  __shared__ __attribute__((aligned(16))) __bf16 Ly[3][RW_YIMG];
+  int bx = (int)blockIdx.x, by = (int)blockIdx.y, bz = (int)blockIdx.z;
+  if (remap & 1) xcd_tile(bx, by, bz);
+  if (remap >> 8) odd_slot_controls(remap);
+  const Geom& g = pl.g;
+  const int k = bz / S, split = bz % S;
+  const int M = pl.M(), N = pl.N(), R = pl.R();
+  const int ktiles = cdiv(R, BK);
+  const int rbeg = (int)((int64_t)ktiles * split / S) * BK;
+  const int rend = std::min(R, (int)((int64_t)ktiles * (split + 1) / S) * BK);
+  const int slot0 = by * TG;
+  const int tid = threadIdx.x;
+  const int wave = tid >> 6, lane = tid & 63;
+  const int wm = wave >> 1, wn = wave & 1;
+  const int h = lane >> 5, l32 = lane & 31;
+  const int HW = g.H * g.W;
+
+  // loads: thread (pixel tid & 63 of the chunk, channels 32 c + 8 (tid >> 6) .. +7): a
+  // wave reads 64 consecutive pixels of one channel per instruction
+  const rsrc_t rx = make_rsrc(pl.x + k * g.sxk, g.xext), ry = make_rsrc(pl.dy + k * g.syk, g.yext);
+  const int lp = tid & 63, cg = tid >> 6;
+  const int sxc4 = (int)g.sxc * 4, syc4 = (int)g.syc * 4;
+  float rxv[2][8], ryv[2][8];
+  auto load = [&](int c0) {
+    const int q = c0 + lp;
+    const uint32_t bb = udiv((uint32_t)q, g.d_hw);
+    const int p = q - (int)bb * HW;
+    const unsigned vx = q < R ? (unsigned)((int)(bb * g.sxb) + p) * 4u + (unsigned)(8 * cg * sxc4) : SENT;
+    const unsigned vy = q < R ? (unsigned)q * 4u + (unsigned)(8 * cg * syc4) : SENT;
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        rxv[c][e] = ld1(rx, vx, (32 * c + e) * sxc4);
+        ryv[c][e] = ld1(ry, vy, (32 * c + e) * syc4);
+      }
+  };
+  // stash: the thread's 16-B chunks (8 channels of its pixel row) of the six images
+  const int sidx = lp * 64 + 8 * (cg ^ tswz(lp));  // channel chunk cg; chunk cg + 4: ^ 32
+  bf16x8 px[2][3], py[2][3];
+  auto split_all = [&]() {
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      split3(rxv[c], px[c][0], px[c][1], px[c][2]);
+      split3(ryv[c], py[c][0], py[c][1], py[c][2]);
+    }
+  };
+  auto write_all = [&]() {
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+      for (int t = 0; t < 3; ++t) {
+        *reinterpret_cast<bf16x8*>(&Lx[t][sidx ^ (32 * c)]) = px[c][t];
+        *reinterpret_cast<bf16x8*>(&Ly[t][sidx ^ (32 * c)]) = py[c][t];
+      }
+  };
+
+  // transposed-read lane addresses (bf16 index in a term image).  This lane supplies
+  // k-row gq of each 4-row block; its 8-k fragment of k-step (kt, s) is the blocks at
+  // chunk pixel 32 kt + 16 s + 8 h + 4 j, j = 0, 1.  dy: the row's swizzle depends on
+  // 4 j + gq only, so (kt, s) is a constant offset.  x: per tap, the shifted row or
+  // the zero row — two 16-bit indices per register.
+  const int gq = (lane & 15) >> 2, gp = lane & 3, g1 = (lane >> 4) & 1;
+  const int ca = 4 * wm + 2 * g1 + (gp >> 1), cb = 4 * wn + 2 * g1 + (gp >> 1);
+  int yoff[2];
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int kk = 8 * h + 4 * j + gq;
+    yoff[j] = kk * 64 + 8 * (cb ^ tswz(kk)) + 4 * (gp & 1);
+  }
+  unsigned xoff[TG][4];
+#pragma unroll
+  for (int t = 0; t < TG; ++t) {
+    int kh, kw;
+    slot_tap(g, slot0 + t, kh, kw);
+    const int dh = uni(kh) - g.pad, dw = uni(kw) - g.pad;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      unsigned pk = 0;
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int pix = 16 * ks + 8 * h + 4 * j + gq;  // chunk pixel; the chunk starts an image
+        const uint32_t bb = udiv((uint32_t)pix, g.d_hw);
+        const int p = pix - (int)bb * HW;
+        const int oh = (int)udiv((uint32_t)p, g.d_w), ow = p - oh * g.W;
+        const int ih = oh + dh, iw = ow + dw;
+        const bool ok = (ih >= 0) & (ih < g.H) & (iw >= 0) & (iw < g.W);
+        const int sr = ok ? pix + dh * g.W + dw : RW_PIX;
+        pk |= (unsigned)(sr * 64 + 8 * (ca ^ tswz(sr)) + 4 * (gp & 1)) << (16 * j);
+      }
+      xoff[t][ks] = pk;
+    }
+  }
+
+  f32x16 acc[TG][1][1];
+#pragma unroll
+  for (int t = 0; t < TG; ++t)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[t][0][0][e] = 0.f;
+  auto tread = [&](const __bf16* img, int o0, int o1) -> bf16x8 {
+    typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + o0));
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4*)(img + o1));
+    typedef short s16x8 __attribute__((ext_vector_type(8)));
+    const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    return __builtin_bit_cast(bf16x8, v);
+  };
+  // the chunk's K-tiles that lie in this part, tap by tap inside a k-step
+  auto compute_chunk = [&](int c0) {
+#pragma unroll
+    for (int kt = 0; kt < 2; ++kt) {
+      const int r0 = c0 + BK * kt;
+      if (r0 < rbeg || r0 >= rend) continue;  // workgroup-uniform
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        const int ks = 2 * kt + s;
+        bf16x8 fy[3];
+#pragma unroll
+        for (int q = 0; q < 3; ++q) fy[q] = tread(Ly[q], yoff[0] + 1024 * ks, yoff[1] + 1024 * ks);
+#pragma unroll
+        for (int t = 0; t < TG; ++t) {
+          bf16x8 fx[3];
+          const int o0 = (int)(xoff[t][ks] & 0xffffu), o1 = (int)(xoff[t][ks] >> 16);
+#pragma unroll
+          for (int q = 0; q < 3; ++q) fx[q] = tread(Lx[q], o0, o1);
+          f32x16 c = acc[t][0][0];
+          // small terms first (term 0 = hi, 1 = mid, 2 = lo)
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fx[1], fy[1], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fx[0], fy[2], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fx[2], fy[0], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fx[0], fy[1], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fx[1], fy[0], c, 0, 0, 0);
+          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fx[0], fy[0], c, 0, 0, 0);
+          acc[t][0][0] = c;
+        }
+      }
+    }
+  };
+  if (rend > rbeg) {
+    const int cbeg = rbeg / RW_PIX * RW_PIX;
+    const int nchunk = (rend - cbeg + RW_PIX - 1) / RW_PIX;
+    const int clast = cbeg + (nchunk - 1) * RW_PIX;
+    load(cbeg);
+    if (tid < 24) {  // the zero row of the three x images: eight 16-B chunks each
+      bf16x8 z;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) z[q] = (__bf16)0.f;
+      *reinterpret_cast<bf16x8*>(&Lx[0][0] + (tid >> 3) * RW_XIMG + RW_PIX * 64 + 8 * (tid & 7)) = z;
+    }
+    split_all();
+    write_all();
+    load(std::min(cbeg + RW_PIX, clast));
+    __syncthreads();
+    // one chunk: its MFMAs from the images and the split of the next chunk; then, once
+    // every wave's fragment reads are done, that chunk's stash and the global loads of
+    // the one after (clamped past the last chunk: duplicates).  Splitting after the
+    // barrier instead measured 116.4–117.7 against 114.9–115.4 us at l1.
+    for (int c = 0; c < nchunk; ++c) {
+      const int c0 = cbeg + c * RW_PIX;
+      compute_chunk(c0);
+      split_all();
+      __syncthreads();
+      write_all();
+      load(std::min(c0 + 2 * RW_PIX, clast));
+      __syncthreads();
+    }
+  }
+  const TileOffs<1, 1> off = sub_tiles<1, 1>(wm, wn);
+#pragma unroll
+  for (int t = 0; t < TG; ++t)
+    store_tiles<Plan, 1, 1>(pl, S, part, k, split, (slot0 + t) * BM, 0, h, l32, M, N, acc[t], off);
+  if constexpr (has_sq<Plan>::value) {
+    if (S == 1 && pl.sq) {  // one slot per (tap, ci) tile: wsgemm_kernel's by * gridDim.x + bx with gridDim.x = 1
+      __shared__ double red[TG][THREADS / 64];
+#pragma unroll
+      for (int t = 0; t < TG; ++t)
+        store_sumsq(pl, k, 0, slot0 + t, (slot0 + t) * BM, 0, h, l32, M, N, acc[t], off, red[t]);
+    }
+  }
+}
+
 template <class Plan>
 __global__ void treduce_kernel(const Plan pl, int S, const float* __restrict__ part) {
   // grid (cdiv(M*N, 256), K): one client per grid row, 32-bit index math
@@ -1023,7 +1240,8 @@ inline int tile_choice(int M, int N, int R) {
 }
 
 template <class Plan, int MS, int NS>
-int launch_tiles(const Plan& pl, void* ws, size_t ws_bytes, hipStream_t st, const char* name, int split_sub = 0) {
+int launch_tiles(const Plan& pl, void* ws, size_t ws_bytes, hipStream_t st, const char* name, int split_sub = 0,
+                 bool wres = false) {
   const int M = pl.M(), N = pl.N(), R = pl.R(), K = pl.g.Kc;
   // split_sub: the sub-tile count the split-K choice is made for (0: this tile's);
   // a launch on smaller tiles with the default tile's split count computes the
@@ -1098,6 +1316,14 @@ int launch_tiles(const Plan& pl, void* ws, size_t ws_bytes, hipStream_t st, cons
 #endif
     if (form == 5) {
       hipLaunchKernelGGL((sgemm_kernel<Plan, MS, NS>), grid, dim3(THREADS), 0, st, pl, S, static_cast<float*>(ws),
+                         xcd_remap());
+      form = -1;
+    }
+  }
+  if constexpr (std::is_same<Plan, WgtT<true>>::value && MS == 1 && NS == 1) {
+    if (form == 5 && wres) {  // wgrad_resident_ok: the same split count, partials and treduce pass
+      const dim3 rgrid(1u, (unsigned)(pl.g.ntaps / RW_TG), (unsigned)(K * S));
+      hipLaunchKernelGGL((rwgemm_kernel<Plan, RW_TG>), rgrid, dim3(THREADS), 0, st, pl, S, static_cast<float*>(ws),
                          xcd_remap());
       form = -1;
     }
@@ -1267,9 +1493,36 @@ int launch_resident(const Plan& pl, hipStream_t st, const char* name) {
   return launch_status(name);
 }
 
+// The resident weight gradient (rwgemm_kernel) for a stride-1 "same" convolution with
+// 64 channels on both sides (one 64 x 64 tile per tap: layer1 of ResNet-18) whose
+// images tile the 64-pixel chunk and whose live taps form whole groups of RW_TG.  The
+// tile, the split count, the partials and the clip-norm slots are the default
+// path's, and so are the bits.  FLR_WGRAD_RESIDENT=0: off (A/B, read per launch).
+inline bool wgrad_resident() {
+  const char* e = flr::knob("FLR_WGRAD_RESIDENT");
+  return !(e && e[0] == '0');
+}
+template <class Plan>
+bool wgrad_resident_ok(const Plan& pl) {
+  if constexpr (!std::is_same<Plan, WgtT<true>>::value) {
+    return false;  // H W % 4 != 0 (WgtT<false>) keeps the default kernel
+  } else {
+    const Geom& g = pl.g;
+    if (!wgrad_resident() || gemm_form() != 5) return false;
+    if (g.stride != 1 || g.Ho != g.H || g.Wo != g.W) return false;
+    if (g.Cin != BM || g.Cout != BN) return false;
+    if (g.ntaps < 2 || g.ntaps % RW_TG != 0) return false;  // one tap: nothing is staged twice
+    if (RW_PIX % (g.H * g.W) != 0) return false;
+    return pl.R() > 0 && plan_tile(pl) == 11;
+  }
+}
+
 template <class Plan>
 int launch(const Plan& pl, void* ws, size_t ws_bytes, hipStream_t st, const char* name) {
   if (pl.R() == 0 && !std::is_same<Plan, DgradT>::value) return FLR_OK;  // a dgrad class with no tap stores zeros
+  if constexpr (std::is_same<Plan, WgtT<true>>::value) {
+    if (wgrad_resident_ok(pl)) return launch_tiles<Plan, 1, 1>(pl, ws, ws_bytes, st, name, 0, true);
+  }
   if constexpr (std::is_same<Plan, FwdT>::value || std::is_same<Plan, DgradT>::value) {
     if (resident_ok(pl)) return launch_resident(pl, st, name);
   }

@@ -1,5 +1,5 @@
 // Tap-major GEMM engine, unit 4 of 5: the weight gradient (WgtT) with its
-// clip-norm partials and the dead-tap zero fill.
+// clip-norm partials, the dead-tap zero fill and the resident form's probe.
 #include "conv_t_kernels.h"
 
 namespace flr {
@@ -34,6 +34,17 @@ extern "C" int64_t flr_conv2d_bwd_weight_t_sq_slots(int64_t K, int64_t B, int64_
   convt::WgtT<true> pl;  // the slot count does not depend on the B-operand load form
   pl.g = conv::make_geom(K, B, Cin, H, W, Cout, KH, KW, stride, pad);
   return pl.R() == 0 ? 0 : convt::sq_slots(pl);
+}
+
+extern "C" int flr_conv2d_wgrad_resident_ok(int64_t K, int64_t B, int64_t Cin, int64_t H, int64_t W, int64_t Cout,
+                                            int64_t KH, int64_t KW, int64_t stride, int64_t pad) {
+  if (!convt::args_ok(K, B, Cin, H, W, Cout, KH, KW, stride, pad)) return 0;
+  const conv::Geom g = conv::make_geom(K, B, Cin, H, W, Cout, KH, KW, stride, pad);
+  if ((g.Ho * g.Wo) % 4 != 0) return 0;  // WgtT<false>
+  convt::WgtT<true> pl;
+  pl.g = g;
+  pl.x = pl.dy = nullptr; pl.dw = nullptr;
+  return convt::wgrad_resident_ok(pl) ? 1 : 0;
 }
 
 extern "C" int flr_conv2d_bwd_weight_t_sq(const float* x, const float* dy, float* dw_t, int64_t K, int64_t B,

@@ -136,6 +136,7 @@ SIGNATURES = {
     "flr_conv2d_bwd_weight_t": (_int, [_c_void_p, _c_void_p, _c_void_p] + [_i64] * 10 + [_int, _c_void_p, _size_t,
                                                                                          _c_void_p]),
     "flr_conv2d_bwd_weight_t_sq_slots": (_i64, [_i64] * 10),
+    "flr_conv2d_wgrad_resident_ok": (_int, [_i64] * 10),
     "flr_conv2d_bwd_weight_t_sq": (_int, [_c_void_p, _c_void_p, _c_void_p] + [_i64] * 10 + [_int, _c_void_p, _i64,
                                                                                             _c_void_p, _size_t,
                                                                                             _c_void_p]),

@@ -1,7 +1,8 @@
 """Per-layer timing of the client-batched conv kernels at the C3 shapes
 (K=128 clients, B=32): fwd / dgrad / wgrad, us and TFLOP/s (useful FLOPs of
 the valid taps).  usage: conv_bench.py [--only NAME] [--reps N] [--resident] [--variants "A=1,B=2;C=3"]
---resident: columns for FLR_CONV_RESIDENT=0 | 1 | 0 | 1 (the resident-B form of layer1's fwd / dgrad).
+--resident: columns for FLR_CONV_RESIDENT=0 | 1 | 0 | 1 (the resident-B form of layer1's fwd / dgrad), then
+for FLR_WGRAD_RESIDENT=0 | 1 | 0 | 1 (the resident form of layer1's weight gradient).
 --variants: extra env settings timed in the same process, interleaved with the
 default (one column each; the kernels read FLR_GEMM / FLR_XCD per launch)."""
 import os, sys, time
@@ -51,6 +52,9 @@ def main():
             variants.append(dict(kv.split("=") for kv in v.split(",") if kv))
     if "--resident" in sys.argv:  # the resident-B form off / on, twice, alternated per op (after the library default)
         variants += [{"FLR_CONV_RESIDENT": v} for v in ("0", "1", "0", "1")]
+        # then the resident weight gradient off / on, twice: only the wgrad row changes kernel over these
+        # four columns, the fwd and dgrad rows show the drift
+        variants += [{"FLR_WGRAD_RESIDENT": v} for v in ("0", "1", "0", "1")]
     print("variants:", variants, flush=True)
     tot = [0.0] * len(variants)
     for name, Cin, H, Cout, k, s, p in LAYERS:
