@@ -434,6 +434,82 @@ int flr_centered_clip(const float* X, int64_t K, int64_t P, int64_t ldx,
                       double* norms_out, float* scales_out, float* tau_out,
                       void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- divide-and-conquer, DnC (Shejwalkar, Houmansadr, NDSS 2021) ---------
+ * "Manipulating the Byzantine", Algorithm 2: the spectral defense of the paper
+ * that Min-Max and Min-Sum (flr_minmax_rows) come from.  No reference
+ * counterpart.  The clients are projected on the top right singular vector of
+ * the centered, column-subsampled client matrix and the nremove largest squared
+ * projections are dropped: it catches attackers that collude along one
+ * direction inside the benign spread, which distances and per-coordinate order
+ * do not.  All niters iterations are enqueued on the stream, no host
+ * synchronisation.  Iteration it = 0 .. niters-1:
+ *   1. columns: b distinct columns of [0, P), ascending, one per stratum:
+ *        lo_j = floor(j*P/b), hi_j = floor((j+1)*P/b),
+ *        col_j = lo_j + h % (hi_j - lo_j),
+ *        h = mix(seed + 0x9E3779B97F4A7C15 * (it*b + j + 1))   (mod 2^64),
+ *        mix(z): z ^= z>>30; z *= 0xBF58476D1CE4E5B9; z ^= z>>27;
+ *                z *= 0x94D049BB133111EB; z ^= z>>31   (splitmix64's finaliser),
+ *      generated on the device.  cols (optional, device int64 [niters][b])
+ *      replaces them: each value is clamped into [0, P-1] on the device; they
+ *      need not be sorted or distinct.
+ *   2. bad rows: a row with a NaN or +-inf among its b sampled values is bad in
+ *      this iteration: left out of the mean, its centered row all zeros, its
+ *      score +inf, never kept.
+ *   3. center, per sampled column, every operation a separately rounded fp32 op
+ *      (no FMA), as flr_collude_rows' mean:
+ *        s = +0.f;  for the good rows i ascending: s = s + x_ij
+ *        mu_j = s / (float)ngood;   c_ij = x_ij - mu_j
+ *   4. Gram: G_ik = sum_j (double)c_ij * (double)c_kj, the products exact in
+ *      fp64, summed in a fixed order (chunks of columns chosen from K and b,
+ *      ascending inside a chunk, the chunks' sums added in order).  The
+ *      singular vector is never formed: for w = G u the projection of row i on
+ *      it is w_i / sqrt(u.w).
+ *   5. power iteration, fp64 (the sums in a fixed order, the same bits from run
+ *      to run):  a = the index of the largest G_aa, the lowest on ties;
+ *        u = G[:,a] / ||G[:,a]||    (the all-ones vector is in G's null space:
+ *                                    C is column-centered)
+ *        power_iters times:  w = G u;  u = w / ||w||
+ *        w = G u;  lam = u.w;  score_i = w_i * w_i / lam
+ *      Every good row scores 0 when G_aa == 0, a ||w|| is 0 or lam <= 0 (one
+ *      client, identical rows).
+ *   6. keep: the K scores ranked ascending, equal scores to the lower index, the
+ *      bad rows last in index order; the iteration keeps the good rows with
+ *      rank < K - nremove.
+ * keep: device int32 [K], 1 for the rows every iteration kept, else 0; when no
+ * row is in that intersection keep is iteration 0's set and bit 0 of flags_out
+ * is set (with every row bad that set is empty too: count 0).  count: device
+ * int32 [1], the number of ones.  Optional device outputs (NULL: not written):
+ * scores_out fp64 [niters][K]; cols_out int64 [niters][b], the columns used;
+ * flags_out int32 [1].  X, columns [P, ldx) included, is only read.
+ * Workspace: flr_dnc_workspace(K, b) bytes (0 for arguments the call rejects),
+ * 256-byte aligned: the compact K x b matrix, G and its partial sums, the
+ * flags.  Bytes moved per iteration: K * b * 4 gathered, the compact matrix
+ * read about 2 + K/8 times from L2.
+ * FLR_ERR_ARG: null X, keep or count; K < 1; b < 1; b > P; ldx < P; niters < 1;
+ * power_iters < 1; nremove outside [0, K-1].  FLR_ERR_UNSUPPORTED: K > 1024
+ * (the spectral kernel is one workgroup, a lane per client), b > 65536,
+ * niters > 16, power_iters > 1024.  FLR_ERR_WORKSPACE: workspace null, too small
+ * or not 256-byte aligned.  Nothing is written on an error. */
+size_t flr_dnc_workspace(int64_t K, int64_t b);
+int flr_dnc_select(const float* X, int64_t K, int64_t P, int64_t ldx, int64_t b,
+                   int64_t niters, int64_t nremove, int64_t power_iters,
+                   uint64_t seed, const int64_t* cols, int32_t* keep,
+                   int32_t* count, double* scores_out, int64_t* cols_out,
+                   int32_t* flags_out, void* workspace, size_t workspace_bytes,
+                   void* stream);
+/* The mean of the rows with keep[i] != 0 (keep: device int32 [K], e.g.
+ * flr_dnc_select's), counted on the device — no host round trip between the
+ * selection and the mean:
+ *   acc = +0.f;  for the kept rows i ascending: acc = acc + x_i;
+ *   out = acc / (float)count           (fp32, every op separately rounded)
+ * bit-identical to flr_rows_mean over the ascending kept list with divisor =
+ * count.  No row kept: 0 / 0, NaN in every coordinate.  Only the kept rows are
+ * read (a NaN in a skipped row leaves out finite); count * P * 4 bytes.
+ * FLR_ERR_ARG: null X, keep or out; K < 1; P < 0; ldx < P.
+ * FLR_ERR_UNSUPPORTED: K > 4096.  Nothing is written on an error. */
+int flr_rows_mean_keep(const float* X, int64_t K, int64_t P, int64_t ldx,
+                       const int32_t* keep, float* out, void* stream);
+
 /* ---- a6 + a7: fused gradient clip + SGD-momentum step -----------------
  * Replaces, for every client row at once, clip_grad_norm_(params, max_norm)
  * + torch.optim.SGD(lr, momentum, weight_decay).step()

@@ -82,6 +82,10 @@ SIGNATURES = {
     "flr_centered_clip_workspace": (_size_t, [_i64, _i64]),
     "flr_centered_clip": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, ctypes.c_float, _i64, _c_void_p, _c_void_p,
                                  _c_void_p, _c_void_p, _c_void_p, _size_t, _c_void_p]),
+    "flr_dnc_workspace": (_size_t, [_i64, _i64]),
+    "flr_dnc_select": (_int, [_c_void_p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_uint64, _c_void_p,
+                              _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _size_t, _c_void_p]),
+    "flr_rows_mean_keep": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p]),
     "flr_clip_sgd_workspace": (_size_t, [_i64]),
     "flr_clip_sgd_step": (_int, [_c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i64, ctypes.c_float, ctypes.c_float,
                                  ctypes.c_float, ctypes.c_float, _int, _c_void_p, _c_void_p, _size_t, _c_void_p]),

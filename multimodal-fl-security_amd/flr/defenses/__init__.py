@@ -6,6 +6,7 @@ Every name of the reference factory is registered and runs on the HIP kernels
 from .base_defense import BaseDefense, NoDefense
 from .bulyan import BulyanDefense
 from .centered_clipping import CenteredClippingDefense
+from .dnc import DnCDefense
 from .krum import KrumDefense, KrumTrimmedMeanDefense, MultiKrumDefense
 from .fltrust import FLTrustDefense
 from .geometric_median import GeometricMedianDefense
@@ -16,6 +17,7 @@ __all__ = [
     "BaseDefense", "NoDefense", "KrumDefense", "MultiKrumDefense", "KrumTrimmedMeanDefense", "BulyanDefense",
     "TrimmedMeanDefense", "MedianDefense", "GeometricMedianDefense",
     "GradientClippingDefense", "NormBoundingDefense", "DPSGDDefense", "FLTrustDefense", "CenteredClippingDefense",
+    "DnCDefense",
     "get_defense",
 ]
 
@@ -37,6 +39,8 @@ _DEFENSES = {
     "bulyan": BulyanDefense,
     # centered clipping (ICML 2021): iterated clipped mean around the previous global model
     "centered_clipping": CenteredClippingDefense,
+    # divide-and-conquer (NDSS 2021): spectral filtering on subsampled coordinates, then the kept rows' mean
+    "dnc": DnCDefense,
 }
 
 

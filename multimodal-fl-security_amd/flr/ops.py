@@ -319,6 +319,64 @@ def centered_clip(X: torch.Tensor, v0: torch.Tensor, tau: float, iters: int, out
     return (out, norms, scales, taus) if diagnostics else out
 
 
+DNC_MAX_ITERS, DNC_MAX_POWER_ITERS = 16, 1024  # flr_dnc_select's limits
+
+
+def dnc_select(X: torch.Tensor, b: int, niters: int, nremove: int, power_iters: int, seed: int = 0,
+               cols: Optional[torch.Tensor] = None, diagnostics: bool = False):
+    """Divide-and-conquer selection (flr_dnc_select): niters times, b sampled
+    columns (generated on the device from seed, or the caller's int64 [niters, b]
+    device tensor cols, clamped into range), centered over the rows; every row
+    scored by its squared projection on the top singular direction (power_iters
+    power steps on the K x K Gram matrix, fp64); the nremove highest scores
+    dropped.  keep marks the rows every iteration kept (iteration 0's set, and
+    bit 0 of flags, when that intersection is empty).  All iterations are
+    enqueued on the current stream: no host synchronisation.  Returns (keep
+    int32 [K], count int32 [1]), or with diagnostics (keep, count, scores float64
+    [niters, K], cols int64 [niters, b], flags int32 [1]) as device tensors."""
+    K, P, ldx = _check_matrix(X)
+    b, niters, nremove, power_iters = int(b), int(niters), int(nremove), int(power_iters)
+    if not 1 <= b <= P:
+        raise ValueError(f"b must be in [1, P = {P}], got {b}")
+    if niters < 1 or power_iters < 1:
+        raise ValueError(f"niters and power_iters must be >= 1, got {niters} and {power_iters}")
+    if not 0 <= nremove <= K - 1:
+        raise ValueError(f"nremove must be in [0, K - 1 = {K - 1}], got {nremove}")
+    if cols is not None and (not isinstance(cols, torch.Tensor) or cols.device != X.device
+                             or cols.dtype != torch.int64 or not cols.is_contiguous()
+                             or tuple(cols.shape) != (niters, b)):
+        raise ValueError(f"cols must be a contiguous int64 [{niters}, {b}] tensor on {X.device}")
+    keep = torch.empty(K, dtype=torch.int32, device=X.device)
+    count = torch.empty(1, dtype=torch.int32, device=X.device)
+    scores = cols_out = flags = None
+    if diagnostics:
+        scores = torch.empty((niters, K), dtype=torch.float64, device=X.device)
+        cols_out = torch.empty((niters, b), dtype=torch.int64, device=X.device)
+        flags = torch.empty(1, dtype=torch.int32, device=X.device)
+    nbytes = int(_capi.lib().flr_dnc_workspace(K, b))
+    ws, wp = _ws(nbytes, X.device)
+    _capi.call("flr_dnc_select", X.data_ptr(), K, P, ldx, b, niters, nremove, power_iters,
+               int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(cols), keep.data_ptr(), count.data_ptr(), _ptr(scores),
+               _ptr(cols_out), _ptr(flags), wp, nbytes, _stream(X))
+    return (keep, count, scores, cols_out, flags) if diagnostics else (keep, count)
+
+
+def rows_mean_keep(X: torch.Tensor, keep: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The mean of the rows with keep != 0 (flr_rows_mean_keep; keep: int32 [K]
+    on X's device, counted there): the bits of rows_mean over the ascending kept
+    rows; NaN everywhere when no row is kept.  Only the kept rows are read."""
+    K, P, ldx = _check_matrix(X)
+    if not isinstance(keep, torch.Tensor) or keep.device != X.device or keep.dtype != torch.int32 \
+            or not keep.is_contiguous() or keep.numel() != K:
+        raise ValueError(f"keep must be a contiguous int32 [{K}] vector on {X.device}")
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=X.device)
+    elif out.device != X.device or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != P:
+        raise ValueError(f"out must be a contiguous float32 [{P}] vector on {X.device}")
+    _capi.call("flr_rows_mean_keep", X.data_ptr(), K, P, ldx, keep.data_ptr(), out.data_ptr(), _stream(X))
+    return out
+
+
 def row_norms(X: torch.Tensor, center: Optional[torch.Tensor] = None, kind: str = "l2") -> torch.Tensor:
     """float64 [K]: ||X_i - center|| per row (l2 or linf); fp32 differences,
     fp64 accumulation in a fixed order (differential_privacy.py:223-236,

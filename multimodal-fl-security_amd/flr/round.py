@@ -132,6 +132,8 @@ class RoundEngine:
         if rcfg.defense in ("krum", "multi_krum", "krum_trimmed_mean", "bulyan"):  # run_experiments.py:155-162
             cfg.setdefault("num_malicious", rcfg.num_attackers)
             cfg.setdefault("multi_k", max(1, K // 2))
+        elif rcfg.defense == "dnc":
+            cfg.setdefault("num_malicious", rcfg.num_attackers)
         self.defense = get_defense(rcfg.defense, cfg)
         mode = rcfg.exchange
         if mode == "auto":
