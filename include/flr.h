@@ -510,6 +510,104 @@ int flr_dnc_select(const float* X, int64_t K, int64_t P, int64_t ldx, int64_t b,
 int flr_rows_mean_keep(const float* X, int64_t K, int64_t P, int64_t ldx,
                        const int32_t* keep, float* out, void* stream);
 
+/* ---- FoolsGold (Fung, Yoon, Beschastnikh, RAID 2020) ----------------------
+ * "The Limitations of Federated Learning in Sybil Settings", Algorithm 1: the
+ * sybil defense.  No reference counterpart.  Clients whose (accumulated) updates
+ * point the same way lose their weight: it needs no attacker count and no server
+ * data, and catches the attackers that act in concert (the colluding attacks'
+ * identical rows, a common backdoor).  Four calls: history, Gram matrix,
+ * weights, combination.  Each enqueues all its work on the stream with no host
+ * synchronisation, never touches columns [P, ld) and writes nothing on an error.
+ *
+ * flr_rows_accumulate, the history update, in place, per element two separately
+ * rounded fp32 operations (no FMA):
+ *   H_ij = fl(H_ij + fl(X_ij - center_j))
+ * H, X: device fp32 K x P (row strides ldh, ldx); center: device fp32 [P].
+ * Bytes moved: 3 * K * P * 4 (H read and written, X read).
+ * FLR_ERR_ARG: null H, X or center; K < 1; P < 1; ldh < P; ldx < P; H == X.
+ * FLR_ERR_UNSUPPORTED: K > 65535. */
+int flr_rows_accumulate(float* H, int64_t ldh, const float* X, int64_t ldx,
+                        const float* center, int64_t K, int64_t P, void* stream);
+/* flr_rows_gram, the K x K Gram matrix of the rows over all P coordinates:
+ *   G_ij = sum_p (double)a_ip * (double)a_jp
+ *   a_ip = A_ip when center is NULL, else fl(A_ip - center_p) (one fp32
+ *          subtraction)
+ * G: device fp64 [K][K], written whole and symmetric: G_ij and G_ji are the same
+ * bits (one sum, stored twice).  The products run on v_mfma_f64_16x16x4_f64 and
+ * are exact (an fp32 converts to fp64 exactly; the product of two has 48
+ * significant bits); the sums are fp64.  The order of the sums is a function of
+ * (K, P) alone, the same on the aligned and the unaligned path, so a rerun gives
+ * the same bits: the columns are cut into flr_rows_gram_splits(K, P) chunks of
+ *   c = max(256, 64 * ceil(ceil(P / max(1, floor(2048 / T))) / 64)) columns,
+ *   T = n (n + 1) / 2, n = ceil(K / 64)     (T <= 136 for K <= 1024)
+ * one workgroup per 64 x 64 block on or above the diagonal and chunk; inside a
+ * chunk the columns go by in groups of 16, MFMA s (0..3) of a group summing its
+ * columns s, s + 4, s + 8, s + 12; a second kernel adds the chunks' partial
+ * entries in chunk order (no second kernel for one chunk).  Blocks below the
+ * diagonal are not computed.  Rows past K and columns past P enter as zeros
+ * through guarded loads; nothing is read past row K - 1 or column P - 1.  Any
+ * lda >= P; rows need no alignment beyond 4 bytes (A and center 16-byte aligned
+ * and lda % 4 == 0: 16-byte loads, the same bits).  A NaN or inf in row i makes
+ * G_ii NaN or inf (the weights' bad-row test).
+ * Workspace: flr_rows_gram_workspace(K, P) bytes (splits * K * K * 8, rounded up
+ * to 256; 0 for one chunk and for arguments the call rejects), 256-byte aligned.
+ * Bytes moved: every 64-row block is read by the n block pairs it is part of,
+ * n * K * P * 4 in all (the pairs of a chunk are adjacent workgroups, so the
+ * repeats mostly come from L2), plus 2 * splits * K * K * 8 for the partial
+ * matrices.
+ * FLR_ERR_ARG: null A or G; K < 1; P < 1; lda < P.  FLR_ERR_UNSUPPORTED: K >
+ * 1024.  FLR_ERR_WORKSPACE (more than one chunk): workspace null, too small or
+ * not 256-byte aligned. */
+size_t flr_rows_gram_workspace(int64_t K, int64_t P);
+int64_t flr_rows_gram_splits(int64_t K, int64_t P); /* 0 for rejected arguments */
+int flr_rows_gram(const float* A, int64_t K, int64_t P, int64_t lda,
+                  const float* center /* may be NULL */, double* G,
+                  void* workspace, size_t workspace_bytes, void* stream);
+/* flr_foolsgold_weights: the clients' weights from the Gram matrix of their
+ * rows.  One workgroup, a lane per client; all arithmetic fp64, in this order:
+ *   row i is bad when G_ii is not finite: alpha_i = 0, it takes no part in
+ *     anyone's maximum; any bad row sets bit 1 of flags.
+ *   n_i = sqrt(G_ii)
+ *   cs_ij = G_ij / (n_i * n_j) for i != j when both rows are good and n_i > 0
+ *     and n_j > 0, else 0; cs_ii = 0 (the original subtracts the identity).  G
+ *     is taken as symmetric: the kernel reads G_ji for cs_ij.
+ *   v_i = max_j cs_ij  (>= 0 because of the diagonal): maxcos_out.
+ *   pardoning: pc_ij = cs_ij * v_i / v_j when v_i < v_j (multiply, then divide),
+ *     else cs_ij.
+ *   w_i = min(1, max(0, 1 - max_j pc_ij))
+ *   top = max_i w_i over the good rows.  top == 0 or every row bad: every
+ *     alpha_i = 0, every beta_i = 0, bit 0 of flags (the paper's "no update").
+ *   else w_i = min(w_i / top, 0.99);
+ *     alpha_i = min(1, max(0, kappa * (log(w_i / (1 - w_i)) + 0.5)))
+ *     (w_i = 0: the logarithm is -inf, alpha_i = 0).
+ *   S = sum_i alpha_i, ascending in i; beta_i = (float)(alpha_i / S); S == 0:
+ *     every beta_i = 0 and bit 0 of flags.
+ *   K = 1: alpha = beta = 1 for a good row.
+ * A maximum ignores a NaN operand.  min(w, 0.99) replaces the original code's
+ * wv[wv == 1] = .99: it is continuous in w, and at the paper's kappa = 1 it
+ * gives the same weights (every w in [0.99, 1) has kappa * (logit + 0.5) > 1
+ * already, so both forms clip to alpha = 1).
+ * alpha: device fp64 [K]; beta: device fp32 [K]; optional (NULL: not written)
+ * maxcos_out fp64 [K], flags_out int32 [1].  Bytes: G read twice (L2).
+ * FLR_ERR_ARG: null G, alpha or beta; K < 1; kappa not a finite number > 0.
+ * FLR_ERR_UNSUPPORTED: K > 1024. */
+int flr_foolsgold_weights(const double* G, int64_t K, double kappa, double* alpha,
+                          float* beta, double* maxcos_out /* optional */,
+                          int32_t* flags_out /* optional */, void* stream);
+/* flr_rows_combine_from: per coordinate, the rows in ascending order, every
+ * operation a separately rounded fp32 op (no FMA), as flr_centered_clip's step:
+ *   acc = +0.f
+ *   for i in 0..K-1:  if beta_i != 0:  acc = acc + (x_i - c) * beta_i
+ *   out = c + acc
+ * beta: device fp32 [K] (flr_foolsgold_weights').  A row with beta_i == 0 is not
+ * read: a NaN in a rejected row leaves out finite.  All beta zero: out == center
+ * bit for bit.  Bytes moved: (rows with beta != 0) * P * 4 read, P * 4 written.
+ * FLR_ERR_ARG: null X, center, beta or out; K < 1; P < 1; ldx < P; out ==
+ * center.  FLR_ERR_UNSUPPORTED: K > 4096. */
+int flr_rows_combine_from(const float* X, int64_t K, int64_t P, int64_t ldx,
+                          const float* center, const float* beta /* device [K] */,
+                          float* out, void* stream);
+
 /* ---- a6 + a7: fused gradient clip + SGD-momentum step -----------------
  * Replaces, for every client row at once, clip_grad_norm_(params, max_norm)
  * + torch.optim.SGD(lr, momentum, weight_decay).step()

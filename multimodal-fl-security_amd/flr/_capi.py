@@ -86,6 +86,13 @@ SIGNATURES = {
     "flr_dnc_select": (_int, [_c_void_p, _i64, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_uint64, _c_void_p,
                               _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p, _size_t, _c_void_p]),
     "flr_rows_mean_keep": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p]),
+    "flr_rows_accumulate": (_int, [_c_void_p, _i64, _c_void_p, _i64, _c_void_p, _i64, _i64, _c_void_p]),
+    "flr_rows_gram_workspace": (_size_t, [_i64, _i64]),
+    "flr_rows_gram_splits": (_i64, [_i64, _i64]),
+    "flr_rows_gram": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _size_t, _c_void_p]),
+    "flr_foolsgold_weights": (_int, [_c_void_p, _i64, ctypes.c_double, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
+                                     _c_void_p]),
+    "flr_rows_combine_from": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "flr_clip_sgd_workspace": (_size_t, [_i64]),
     "flr_clip_sgd_step": (_int, [_c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i64, ctypes.c_float, ctypes.c_float,
                                  ctypes.c_float, ctypes.c_float, _int, _c_void_p, _c_void_p, _size_t, _c_void_p]),

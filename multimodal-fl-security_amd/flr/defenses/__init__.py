@@ -9,6 +9,7 @@ from .centered_clipping import CenteredClippingDefense
 from .dnc import DnCDefense
 from .krum import KrumDefense, KrumTrimmedMeanDefense, MultiKrumDefense
 from .fltrust import FLTrustDefense
+from .foolsgold import FoolsGoldDefense
 from .geometric_median import GeometricMedianDefense
 from .norm_based import DPSGDDefense, GradientClippingDefense, NormBoundingDefense
 from .trimmed_mean import MedianDefense, TrimmedMeanDefense
@@ -17,7 +18,7 @@ __all__ = [
     "BaseDefense", "NoDefense", "KrumDefense", "MultiKrumDefense", "KrumTrimmedMeanDefense", "BulyanDefense",
     "TrimmedMeanDefense", "MedianDefense", "GeometricMedianDefense",
     "GradientClippingDefense", "NormBoundingDefense", "DPSGDDefense", "FLTrustDefense", "CenteredClippingDefense",
-    "DnCDefense",
+    "DnCDefense", "FoolsGoldDefense",
     "get_defense",
 ]
 
@@ -41,6 +42,8 @@ _DEFENSES = {
     "centered_clipping": CenteredClippingDefense,
     # divide-and-conquer (NDSS 2021): spectral filtering on subsampled coordinates, then the kept rows' mean
     "dnc": DnCDefense,
+    # FoolsGold (RAID 2020): sybils resemble each other; weights from the clients' pairwise cosine similarity
+    "foolsgold": FoolsGoldDefense,
 }
 
 

@@ -377,6 +377,112 @@ def rows_mean_keep(X: torch.Tensor, keep: torch.Tensor, out: Optional[torch.Tens
     return out
 
 
+FOOLSGOLD_MAX_CLIENTS = 1024  # flr_rows_gram's and flr_foolsgold_weights' limit
+
+
+def _check_vector(t, n: int, device, name: str, dtype=torch.float32) -> None:
+    if not isinstance(t, torch.Tensor) or t.device != device or t.dtype != dtype or not t.is_contiguous() \
+            or t.numel() != n:
+        raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} [{n}] vector on {device}")
+
+
+def rows_accumulate_(H: torch.Tensor, X: torch.Tensor, center: torch.Tensor) -> torch.Tensor:
+    """H += X - center in place (flr_rows_accumulate): per element
+    fl(H + fl(X - center)), two fp32 operations.  H, X: [K, P] row-major
+    matrices (any row strides), center: [P].  Returns H."""
+    K, P, ldh = _check_matrix(H, "H")
+    K2, P2, ldx = _check_matrix(X)
+    if (K2, P2) != (K, P) or X.device != H.device:
+        raise ValueError(f"H is {K} x {P} on {H.device}, X {K2} x {P2} on {X.device}")
+    if K < 1 or P < 1:
+        raise ValueError(f"rows_accumulate_ needs K >= 1 and P >= 1, got {K} x {P}")
+    _check_vector(center, P, H.device, "center")
+    _capi.call("flr_rows_accumulate", H.data_ptr(), ldh, X.data_ptr(), ldx, center.data_ptr(), K, P, _stream(H))
+    return H
+
+
+def rows_gram(A: torch.Tensor, center: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float64 [K, K]: G = A A^T over all P coordinates (flr_rows_gram), of the
+    rows minus center when one is given (one fp32 subtraction): the products
+    exact on the fp64 matrix cores, the fp64 sums in an order fixed by (K, P);
+    G is symmetric bit for bit.  K <= 1024."""
+    K, P, lda = _check_matrix(A, "A")
+    if K < 1 or P < 1:
+        raise ValueError(f"rows_gram needs K >= 1 and P >= 1, got {K} x {P}")
+    if K > FOOLSGOLD_MAX_CLIENTS:
+        raise ValueError(f"rows_gram handles at most {FOOLSGOLD_MAX_CLIENTS} rows, got {K}")
+    if center is not None:
+        _check_vector(center, P, A.device, "center")
+    if out is None:
+        out = torch.empty((K, K), dtype=torch.float64, device=A.device)
+    elif not isinstance(out, torch.Tensor) or out.device != A.device or out.dtype != torch.float64 \
+            or not out.is_contiguous() or tuple(out.shape) != (K, K):
+        raise ValueError(f"out must be a contiguous float64 [{K}, {K}] matrix on {A.device}")
+    nbytes = int(_capi.lib().flr_rows_gram_workspace(K, P))
+    ws, wp = _ws(nbytes, A.device)
+    _capi.call("flr_rows_gram", A.data_ptr(), K, P, lda, _ptr(center), out.data_ptr(), wp, nbytes, _stream(A))
+    return out
+
+
+def rows_gram_splits(K: int, P: int) -> int:
+    """The column chunks of rows_gram's sum at (K, P) (flr_rows_gram_splits)."""
+    return int(_capi.lib().flr_rows_gram_splits(int(K), int(P)))
+
+
+def foolsgold_weights(G: torch.Tensor, kappa: float = 1.0, diagnostics: bool = False):
+    """FoolsGold's client weights from the Gram matrix of the client rows
+    (flr_foolsgold_weights; the arithmetic in include/flr.h): alpha float64 [K]
+    in [0, 1] and beta = float32(alpha / sum(alpha)), all zero for "no update".
+    Returns (alpha, beta), or with diagnostics (alpha, beta, max_cosine float64
+    [K], flags int32 [1]: bit 0 no update, bit 1 a row with a non-finite norm)
+    as device tensors."""
+    if not isinstance(G, torch.Tensor) or not G.is_cuda:
+        raise RuntimeError("G must be a CUDA/HIP tensor (the engine has no CPU path)")
+    if G.dtype != torch.float64 or G.dim() != 2 or G.shape[0] != G.shape[1] or not G.is_contiguous():
+        raise ValueError(f"G must be a contiguous float64 [K, K] matrix (got {G.dtype}, shape {tuple(G.shape)})")
+    K = G.shape[0]
+    if K < 1:
+        raise ValueError("foolsgold_weights needs K >= 1")
+    if K > FOOLSGOLD_MAX_CLIENTS:
+        raise ValueError(f"foolsgold_weights handles at most {FOOLSGOLD_MAX_CLIENTS} clients, got {K}")
+    kappa = float(kappa)
+    if not 0.0 < kappa < float("inf"):
+        raise ValueError(f"kappa must be a finite number > 0, got {kappa}")
+    alpha = torch.empty(K, dtype=torch.float64, device=G.device)
+    beta = torch.empty(K, dtype=torch.float32, device=G.device)
+    maxcos = flags = None
+    if diagnostics:
+        maxcos = torch.empty(K, dtype=torch.float64, device=G.device)
+        flags = torch.empty(1, dtype=torch.int32, device=G.device)
+    _capi.call("flr_foolsgold_weights", G.data_ptr(), K, kappa, alpha.data_ptr(), beta.data_ptr(), _ptr(maxcos),
+               _ptr(flags), _stream(G))
+    return (alpha, beta, maxcos, flags) if diagnostics else (alpha, beta)
+
+
+def rows_combine_from(X: torch.Tensor, center: torch.Tensor, beta: torch.Tensor,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """out = center + sum_i (X_i - center) * beta_i (flr_rows_combine_from): fp32,
+    the rows in ascending order, every op separately rounded; rows with beta_i
+    == 0 are not read; all beta zero gives center's bits.  beta: float32 [K] on
+    X's device.  out must not be center."""
+    K, P, ldx = _check_matrix(X)
+    if K < 1 or P < 1:
+        raise ValueError(f"rows_combine_from needs K >= 1 and P >= 1, got {K} x {P}")
+    if K > 4096:
+        raise ValueError(f"rows_combine_from handles at most 4096 rows, got {K}")
+    _check_vector(center, P, X.device, "center")
+    _check_vector(beta, K, X.device, "beta")
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=X.device)
+    else:
+        _check_vector(out, P, X.device, "out")
+        if out.data_ptr() == center.data_ptr():
+            raise ValueError("out must not be center")
+    _capi.call("flr_rows_combine_from", X.data_ptr(), K, P, ldx, center.data_ptr(), beta.data_ptr(), out.data_ptr(),
+               _stream(X))
+    return out
+
+
 def row_norms(X: torch.Tensor, center: Optional[torch.Tensor] = None, kind: str = "l2") -> torch.Tensor:
     """float64 [K]: ||X_i - center|| per row (l2 or linf); fp32 differences,
     fp64 accumulation in a fixed order (differential_privacy.py:223-236,
