@@ -22,34 +22,17 @@
 // K * P * 4 bytes and writes P * 4): one lane per float4 of coordinates — each
 // load instruction reads 1 KiB contiguous bytes of one row — with a scalar lane
 // per coordinate of the P mod 4 tail; one lane per coordinate when X, v or out is
-// not 16-B aligned or ldx % 4 != 0.  The rows are streamed with 16 loads in
-// flight per lane; the K scales sit in LDS and reach the lanes as one
+// not 16-B aligned or ldx % 4 != 0 (rows_pass.h's lane map).  The rows are streamed
+// with 16 loads in flight per lane (its stream_rows); the K scales sit in LDS and reach the lanes as one
 // wave-uniform value per row, so the skip is a scalar branch.  The iterates
 // alternate between out and a P-vector of the workspace, the last one in out.
-#include "flr_common.h"
+#include "rows_pass.h"
 
 namespace flr {
 namespace cclip {
 
-constexpr int THREADS = 256;
-constexpr int STREAM = 16;     // loads in flight per lane
+using namespace rows;          // THREADS, STREAM, the lane map, the row stream (rows_pass.h)
 constexpr int MAXROWS = 4096;  // the scales in LDS; flr_weighted_rows' limit
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
-
-// The value of lane 0 in an SGPR: tells the compiler it is wave-uniform.
-__device__ __forceinline__ float uniform(float x) {
-  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x)));
-}
-
-// Ascending order of the floats as unsigned keys, NaN (either sign) last.
-__device__ __forceinline__ uint32_t sort_key(float x) {
-  if (x != x) return 0xffffffffu;
-  const uint32_t u = __float_as_uint(x);
-  return (u >> 31) ? ~u : (u | 0x80000000u);
-}
 
 // One workgroup.  t and the K scales from the K distances; tau == 0: t is the
 // lower median by rank counting (each row's rank = the keys below it, equal keys
@@ -63,15 +46,8 @@ __global__ __launch_bounds__(THREADS) void scales_kernel(const double* __restric
     for (int i = threadIdx.x; i < K; i += THREADS) key[i] = sort_key((float)d[i]);
     __syncthreads();
     const int m = (K - 1) / 2;
-    for (int i = threadIdx.x; i < K; i += THREADS) {
-      const uint32_t ki = key[i];
-      int r = 0;
-      for (int j = 0; j < K; ++j) {
-        const uint32_t kj = key[j];
-        r += (kj < ki || (kj == ki && j < i)) ? 1 : 0;
-      }
-      if (r == m) tmed = (float)d[i];  // the ranks are a permutation: one writer
-    }
+    for (int i = threadIdx.x; i < K; i += THREADS)
+      if (rank_below(key, K, i) == m) tmed = (float)d[i];  // the ranks are a permutation: one writer
     __syncthreads();
     t = tmed;
   }
@@ -82,20 +58,7 @@ __global__ __launch_bounds__(THREADS) void scales_kernel(const double* __restric
   }
 }
 
-template <int W>
-__device__ __forceinline__ void load(const float* __restrict__ p, float (&x)[W]) {
-  if constexpr (W == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = t[e];
-  } else {
-    x[0] = *p;
-  }
-}
-
-// W adjacent coordinates from p on: the rows in groups of STREAM loads; the last,
-// partial group re-reads the last row instead of testing each load (the loads
-// issue back to back) and tests each use.
+// W adjacent coordinates from p on, the rows streamed (stream_rows).
 template <int W>
 __device__ __forceinline__ void step_columns(const float* __restrict__ X, int K, int64_t ldx, int64_t p,
                                              const float* __restrict__ v, const float* ss,
@@ -104,49 +67,20 @@ __device__ __forceinline__ void step_columns(const float* __restrict__ X, int K,
   load<W>(v + p, c);
 #pragma unroll
   for (int e = 0; e < W; ++e) acc[e] = 0.f;
-  const float* col = X + p;
-  const int nfull = K - K % STREAM;
-  for (int k0 = 0; k0 < nfull; k0 += STREAM) {
-    float t[STREAM][W];
+  stream_rows<W>(X + p, ldx, K, [](int k) { return k; }, [&](int k, const float(&x)[W]) {
+    const float sk = uniform(ss[k]);
+    if (sk != 0.f) {
 #pragma unroll
-    for (int i = 0; i < STREAM; ++i) load<W>(col + (int64_t)(k0 + i) * ldx, t[i]);
-#pragma unroll
-    for (int i = 0; i < STREAM; ++i) {
-      const float si = uniform(ss[k0 + i]);
-      if (si != 0.f) {
-#pragma unroll
-        for (int e = 0; e < W; ++e) acc[e] = add_rn(acc[e], mul_rn(sub_rn(t[i][e], c[e]), si));
-      }
+      for (int e = 0; e < W; ++e) acc[e] = add_rn(acc[e], mul_rn(sub_rn(x[e], c[e]), sk));
     }
-  }
-  if (nfull < K) {
-    float t[STREAM][W];
-#pragma unroll
-    for (int i = 0; i < STREAM; ++i) load<W>(col + (int64_t)min(nfull + i, K - 1) * ldx, t[i]);
-#pragma unroll
-    for (int i = 0; i < STREAM; ++i) {
-      if (nfull + i < K) {
-        const float si = uniform(ss[nfull + i]);
-        if (si != 0.f) {
-#pragma unroll
-          for (int e = 0; e < W; ++e) acc[e] = add_rn(acc[e], mul_rn(sub_rn(t[i][e], c[e]), si));
-        }
-      }
-    }
-  }
+  });
   const float fk = (float)K;
-  if constexpr (W == 4) {
-    f32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = add_rn(c[e], div_rn(acc[e], fk));
-    *reinterpret_cast<f32x4*>(out + p) = o;
-  } else {
-    out[p] = add_rn(c[0], div_rn(acc[0], fk));
-  }
+  for (int e = 0; e < W; ++e) acc[e] = add_rn(c[e], div_rn(acc[e], fk));
+  store<W>(out + p, acc);
 }
 
-// VEC: lane q < P / 4 owns coordinates [4q, 4q + 4), the next P % 4 lanes one
-// coordinate of the tail each; otherwise lane q owns coordinate q.
+// One lane of the lane map (lane_columns) per workgroup lane.
 template <bool VEC>
 __global__ __launch_bounds__(THREADS) void step_kernel(const float* __restrict__ X, int K, int64_t P, int64_t ldx,
                                                        const float* __restrict__ v, const float* __restrict__ s,
@@ -154,14 +88,9 @@ __global__ __launch_bounds__(THREADS) void step_kernel(const float* __restrict__
   __shared__ float ss[MAXROWS];
   for (int t = threadIdx.x; t < K; t += THREADS) ss[t] = s[t];
   __syncthreads();
-  const int64_t q = (int64_t)blockIdx.x * THREADS + threadIdx.x;
-  if constexpr (VEC) {
-    const int64_t nv = P / 4;
-    if (q < nv) step_columns<4>(X, K, ldx, 4 * q, v, ss, out);
-    else if (q < nv + (P & 3)) step_columns<1>(X, K, ldx, 4 * nv + (q - nv), v, ss, out);
-  } else {
-    if (q < P) step_columns<1>(X, K, ldx, q, v, ss, out);
-  }
+  lane_columns<VEC>((int64_t)blockIdx.x * THREADS + threadIdx.x, P, [&](auto w, int64_t p) {
+    step_columns<decltype(w)::value>(X, K, ldx, p, v, ss, out);
+  });
 }
 
 // The workspace: the row_norms partials, then K distances, K scales and the
@@ -194,10 +123,8 @@ extern "C" int flr_centered_clip(const float* X, int64_t K, int64_t P, int64_t l
       (reinterpret_cast<uintptr_t>(workspace) & 255) != 0)
     return FLR_ERR_WORKSPACE;
   if (K > cclip::MAXROWS) return FLR_ERR_UNSUPPORTED;
-  const bool vec = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(v0) |
-                     reinterpret_cast<uintptr_t>(out)) & 15) == 0 && ldx % 4 == 0;
-  const int64_t lanes = vec ? P / 4 + (P & 3) : P;
-  const int64_t nblocks = (lanes + cclip::THREADS - 1) / cclip::THREADS;
+  const bool vec = rows::vec_ok(X, v0, out, ldx);
+  const int64_t nblocks = (rows::column_lanes(vec, P) + cclip::THREADS - 1) / cclip::THREADS;
   if (nblocks > 0x7fffffffLL) return FLR_ERR_UNSUPPORTED;
   hipStream_t st = as_stream(stream);
   const cclip::Layout lay(K, P);

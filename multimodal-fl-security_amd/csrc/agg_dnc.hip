@@ -20,35 +20,26 @@
 //   gram      16 x 16 output tiles, 64-column LDS tiles, one fp64 lane per entry;
 //             the columns cut into chunks (a function of K and b) so that a
 //             small K still fills the device, each chunk summed in ascending
-//             order, then the chunks' sums added in chunk order
+//             order, then the chunks' sums added in chunk order (rows_pass.h's
+//             ColumnChunks and gram_reduce)
 //   spectral  one workgroup: the power iteration on G (read through its
 //             transpose — G is symmetric bit for bit — so the lanes' loads
 //             coalesce; the sum over k split into wave-uniform slices combined
 //             in slice order; K <= 128: a lane's entries of G stay in
 //             registers), the scores, the rank-count selection and the AND into
 //             keep; the last iteration counts and applies the fallback.
-// flr_rows_mean_keep is the HBM-bound pass: the kept rows' ascending list is
-// compacted into LDS by one wave (ballot + popcount), then flr_rows_mean's sum
-// with 16 loads in flight per lane — only kept rows are read.
-#include "flr_common.h"
+// The aggregate, the mean of the kept rows, is flr_rows_mean_keep (agg_mean.hip).
+#include "rows_pass.h"
 
 namespace flr {
 namespace dnc {
 
-constexpr int THREADS = 256;
-constexpr int STREAM = 16;  // loads in flight per lane
+using namespace rows;  // THREADS, STREAM, the row stream, block_reduce, the rank count (rows_pass.h)
 constexpr int MAXK = 1024, MAXB = 65536, MAXITERS = 16, MAXPOWER = 1024;
 constexpr int SPEC_THREADS = 1024;  // the spectral workgroup: one lane per client
 constexpr int SPEC_WAVES = SPEC_THREADS / 64;
-constexpr int KEEP_MAXROWS = 4096;  // flr_rows_mean's row limit
-constexpr int GT = 16, GJ = 64;     // Gram: output tile edge, columns per LDS tile
+constexpr int GT = 16, GJ = 64;  // Gram: output tile edge, columns per LDS tile
 constexpr int CENTER_THREADS = 64;
-constexpr int GRAM_BLOCKS = 2048;   // Gram: the workgroups the column chunks are chosen to reach
-constexpr int GRAM_MIN_CHUNK = 4 * GJ;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
 
 __device__ __forceinline__ bool non_finite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
 
@@ -83,6 +74,8 @@ __global__ __launch_bounds__(THREADS) void gather_kernel(const float* __restrict
     c = (int64_t)(lo + h % (hi - lo));
   }
   if (cols_out && blockIdx.y == 0) cols_out[j] = c;
+  // one clamped group and no row loop: stream_rows would compile its full-group
+  // and its partial-group body for a lane that runs one of them once
   const float* col = X + c;
   const int k0 = blockIdx.y * STREAM;
   float t[STREAM];
@@ -98,9 +91,8 @@ __global__ __launch_bounds__(THREADS) void gather_kernel(const float* __restrict
 }
 
 // Lane j: column j of C <- x - mu over the good rows, zeros in the bad rows.  The
-// adds are a chain, the loads are not: groups of STREAM loads issue together
-// (the last group re-reads the last row and tests each use).  One wave per
-// workgroup, so that b columns reach b / 64 compute units.
+// adds are a chain, the loads are not: the rows are streamed (stream_rows), twice.
+// One wave per workgroup, so that b columns reach b / 64 compute units.
 __global__ __launch_bounds__(CENTER_THREADS) void center_kernel(float* __restrict__ C, int K, int b,
                                                          const int32_t* __restrict__ bad) {
   __shared__ int32_t sb[MAXK];
@@ -117,41 +109,22 @@ __global__ __launch_bounds__(CENTER_THREADS) void center_kernel(float* __restric
   const int j = blockIdx.x * CENTER_THREADS + threadIdx.x;
   if (j >= b) return;
   float* col = C + j;
+  const auto row = [](int k) { return k; };
   float s = 0.f;
-  for (int k0 = 0; k0 < K; k0 += STREAM) {
-    float t[STREAM];
-#pragma unroll
-    for (int i = 0; i < STREAM; ++i) t[i] = col[(int64_t)min(k0 + i, K - 1) * b];
-#pragma unroll
-    for (int i = 0; i < STREAM; ++i)
-      if (k0 + i < K && !sb[k0 + i]) s = add_rn(s, t[i]);
-  }
+  stream_rows<1>(col, b, K, row, [&](int k, const float(&x)[1]) {
+    if (!sb[k]) s = add_rn(s, x[0]);
+  });
   const float mu = div_rn(s, (float)ngood_s);
-  for (int k0 = 0; k0 < K; k0 += STREAM) {
-    float t[STREAM];
-#pragma unroll
-    for (int i = 0; i < STREAM; ++i) t[i] = col[(int64_t)min(k0 + i, K - 1) * b];
-#pragma unroll
-    for (int i = 0; i < STREAM; ++i)
-      if (k0 + i < K) col[(int64_t)(k0 + i) * b] = sb[k0 + i] ? 0.f : sub_rn(t[i], mu);
-  }
+  stream_rows<1>(col, b, K, row, [&](int k, const float(&x)[1]) {  // a group's loads precede its stores
+    col[(int64_t)k * b] = sb[k] ? 0.f : sub_rn(x[0], mu);
+  });
 }
 
-// The Gram sum's column chunks: a K x K matrix has few 16 x 16 tiles (64 at K =
-// 128), so the columns are cut into chunks of whole LDS tiles, about GRAM_BLOCKS
-// workgroups in all and at least GRAM_MIN_CHUNK columns each.  A function of (K,
-// b) alone: the summation order is the same from run to run.
-struct GramPlan {
-  int chunk, splits;
-  GramPlan(int64_t K, int64_t b) {
-    const int64_t side = (K + GT - 1) / GT, want = GRAM_BLOCKS / (side * side);
-    int64_t c = want < 1 ? b : (b + want - 1) / want;
-    c = (c + GJ - 1) / GJ * GJ;
-    if (c < GRAM_MIN_CHUNK) c = GRAM_MIN_CHUNK;
-    chunk = (int)c;
-    splits = (int)((b + c - 1) / c);
-  }
-};
+// The Gram sum's column chunks (ColumnChunks) over the 16 x 16 output tiles.
+inline ColumnChunks gram_chunks(int64_t K, int64_t b) {
+  const int64_t side = (K + GT - 1) / GT;
+  return ColumnChunks(side * side, b, GJ);
+}
 
 // G = C C^T.  Workgroup (bx, by, bz): the 16 x 16 tile at rows 16*by, columns
 // 16*bx, over the columns of chunk bz; lane (ty, tx) sums its entry over them in
@@ -194,62 +167,12 @@ __global__ __launch_bounds__(GT * GT) void gram_kernel(const float* __restrict__
   if (i0 + ty < K && k0 + tx < K) dst[(int64_t)blockIdx.z * K * K + (int64_t)(i0 + ty) * K + k0 + tx] = acc;
 }
 
-// G = the chunks' partial matrices added in chunk order.
-__global__ __launch_bounds__(THREADS) void gram_reduce_kernel(const double* __restrict__ part, int splits, int n,
-                                                              double* __restrict__ G) {
-  const int e = blockIdx.x * THREADS + threadIdx.x;
-  if (e >= n) return;
-  double s = 0.0;
-#pragma unroll 8
-  for (int z = 0; z < splits; ++z) s += part[(int64_t)z * n + e];
-  G[e] = s;
-}
-
-// Workgroup-wide reductions; every lane gets the same bits (the butterfly adds
-// the same pairs in every lane, then each lane adds the wave results in order).
+// Workgroup-wide reductions (block_reduce): every lane gets the same bits.
 __device__ __forceinline__ double block_sum(double v, double* red) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int w = 0; w < SPEC_WAVES; ++w) s += red[w];
-  return s;
-}
-__device__ __forceinline__ double block_max(double v, double* red) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = fmax(v, __shfl_xor(v, m));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = red[0];
-#pragma unroll
-  for (int w = 1; w < SPEC_WAVES; ++w) s = fmax(s, red[w]);
-  return s;
-}
-__device__ __forceinline__ int block_min(int v, int* red) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v = min(v, __shfl_xor(v, m));
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int s = red[0];
-#pragma unroll
-  for (int w = 1; w < SPEC_WAVES; ++w) s = min(s, red[w]);
-  return s;
+  return block_reduce<SPEC_WAVES>(v, red, [](double a, double o) { return a + o; });
 }
 __device__ __forceinline__ int block_count(int v, int* red) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int s = 0;
-#pragma unroll
-  for (int w = 0; w < SPEC_WAVES; ++w) s += red[w];
-  return s;
+  return block_reduce<SPEC_WAVES>(v, red, [](int a, int o) { return a + o; });
 }
 
 // The power iteration from u (LDS, all MAXK entries defined and synchronised):
@@ -306,12 +229,10 @@ __device__ __forceinline__ bool power_scores(const double* __restrict__ G, int K
 }
 
 // Ascending order of the doubles as unsigned keys; NaN above +inf, a bad row
-// above everything.
+// above everything: NaN's shared key, all ones, moves one down to make room.
 __device__ __forceinline__ uint64_t sort_key(double x, bool bad) {
-  if (bad) return 0xffffffffffffffffull;
-  if (x != x) return 0xfffffffffffffffeull;
-  const uint64_t u = (uint64_t)__double_as_longlong(x);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+  const uint64_t nan = 0xffffffffffffffffull, k = rows::sort_key(x);
+  return bad ? nan : (k == nan ? nan - 1 : k);
 }
 
 // One workgroup, lane t = client t.  The scores of iteration `it` from G, its
@@ -333,8 +254,9 @@ __global__ __launch_bounds__(SPEC_THREADS) void spectral_kernel(const double* __
   const bool isbad = row && bad[t] != 0;
 
   const double diag = row ? G[(int64_t)t * K + t] : -1.0;
-  const double gaa = block_max(diag, red);
-  const int a = block_min(row && diag == gaa ? t : K, ired);  // the lowest index of the largest entry
+  const double gaa = block_reduce<SPEC_WAVES>(diag, red, [](double a, double o) { return fmax(a, o); });
+  // the lowest index of the largest entry
+  const int a = block_reduce<SPEC_WAVES>(row && diag == gaa ? t : K, ired, [](int a, int o) { return min(a, o); });
   bool degenerate = a >= K || gaa == 0.0;
   double score = 0.0;
   if (!degenerate) {  // every branch below is uniform over the workgroup
@@ -352,15 +274,7 @@ __global__ __launch_bounds__(SPEC_THREADS) void spectral_kernel(const double* __
   }
   __syncthreads();
   int kept = 0;
-  if (row) {
-    const uint64_t kt = key[t];
-    int r = 0;
-    for (int j = 0; j < K; ++j) {
-      const uint64_t kj = key[j];
-      r += (kj < kt || (kj == kt && j < t)) ? 1 : 0;
-    }
-    kept = (!isbad && r < K - nremove) ? 1 : 0;
-  }
+  if (row) kept = (!isbad && rank_below(key, K, t) < K - nremove) ? 1 : 0;
   const int first = row ? (it == 0 ? kept : keep0[t]) : 0;  // iteration 0's set
   int kp = row ? (it == 0 ? kept : (kept & (keep[t] != 0 ? 1 : 0))) : 0;
   if (row && it == 0 && !last) keep0[t] = kept;
@@ -380,105 +294,13 @@ __global__ __launch_bounds__(SPEC_THREADS) void spectral_kernel(const double* __
   if (row) keep[t] = kp;
 }
 
-template <int W>
-__device__ __forceinline__ void load(const float* __restrict__ p, float (&x)[W]) {
-  if constexpr (W == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = t[e];
-  } else {
-    x[0] = *p;
-  }
-}
-
-// W adjacent coordinates from p on: the m listed rows in groups of STREAM loads;
-// the last, partial group re-reads the last listed row instead of testing each
-// load and tests each use; a row index is one wave-uniform value.  m == 0: 0 / 0.
-template <int W>
-__device__ __forceinline__ void mean_columns(const float* __restrict__ X, int64_t ldx, int64_t p, const int32_t* rs,
-                                             int m, float fm, float* __restrict__ out) {
-  float acc[W];
-#pragma unroll
-  for (int e = 0; e < W; ++e) acc[e] = 0.f;
-  const float* col = X + p;
-  const int nfull = m - m % STREAM;
-  for (int k0 = 0; k0 < nfull; k0 += STREAM) {
-    float t[STREAM][W];
-#pragma unroll
-    for (int i = 0; i < STREAM; ++i) load<W>(col + (int64_t)__builtin_amdgcn_readfirstlane(rs[k0 + i]) * ldx, t[i]);
-#pragma unroll
-    for (int i = 0; i < STREAM; ++i) {
-#pragma unroll
-      for (int e = 0; e < W; ++e) acc[e] = add_rn(acc[e], t[i][e]);
-    }
-  }
-  if (nfull < m) {
-    float t[STREAM][W];
-#pragma unroll
-    for (int i = 0; i < STREAM; ++i) load<W>(col + (int64_t)__builtin_amdgcn_readfirstlane(rs[min(nfull + i, m - 1)]) * ldx, t[i]);
-#pragma unroll
-    for (int i = 0; i < STREAM; ++i) {
-      if (nfull + i < m) {
-#pragma unroll
-        for (int e = 0; e < W; ++e) acc[e] = add_rn(acc[e], t[i][e]);
-      }
-    }
-  }
-  if constexpr (W == 4) {
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = div_rn(acc[e], fm);
-    *reinterpret_cast<f32x4*>(out + p) = o;
-  } else {
-    out[p] = div_rn(acc[0], fm);
-  }
-}
-
-// The mean of the rows with keep != 0.  Wave 0 compacts their indices, ascending,
-// into LDS (ballot + popcount per 64 rows): the row loop reads kept rows only, a
-// wave-uniform index per load.  VEC: lane q < P / 4 owns coordinates [4q, 4q + 4),
-// the next P % 4 lanes one coordinate of the tail each; otherwise lane q owns
-// coordinate q.
-template <bool VEC>
-__global__ __launch_bounds__(THREADS) void rows_mean_keep_kernel(const float* __restrict__ X, int K, int64_t P,
-                                                                 int64_t ldx, const int32_t* __restrict__ keep,
-                                                                 float* __restrict__ out) {
-  __shared__ int32_t rs[KEEP_MAXROWS];
-  __shared__ int m_s;
-  if (threadIdx.x < 64) {
-    int base = 0;
-    for (int i0 = 0; i0 < K; i0 += 64) {
-      const int i = i0 + (int)threadIdx.x;
-      const bool k = i < K && keep[i] != 0;
-      const unsigned long long mask = __ballot(k);
-      if (k) rs[base + __popcll(mask & ((1ull << threadIdx.x) - 1ull))] = i;
-      base += __popcll(mask);
-    }
-    if (threadIdx.x == 0) m_s = base;
-  }
-  __syncthreads();
-  const int m = m_s;
-  const float fm = (float)m;
-  const int64_t stride = (int64_t)gridDim.x * THREADS;
-  if constexpr (VEC) {
-    const int64_t nv = P / 4, lanes = nv + (P & 3);
-    for (int64_t q = (int64_t)blockIdx.x * THREADS + threadIdx.x; q < lanes; q += stride) {
-      if (q < nv) mean_columns<4>(X, ldx, 4 * q, rs, m, fm, out);
-      else mean_columns<1>(X, ldx, 4 * nv + (q - nv), rs, m, fm, out);
-    }
-  } else {
-    for (int64_t q = (int64_t)blockIdx.x * THREADS + threadIdx.x; q < P; q += stride)
-      mean_columns<1>(X, ldx, q, rs, m, fm, out);
-  }
-}
-
 // The workspace: the compact K x b matrix, G, the column chunks' partial
 // matrices (none for one chunk), the bad flags of every iteration (cleared by
 // one memset per call) and iteration 0's kept set, each 256-B aligned.
 struct Layout {
   size_t c, g, part, bad, keep0, total;
   Layout(int64_t K, int64_t b) {
-    const GramPlan plan(K, b);
+    const ColumnChunks plan = gram_chunks(K, b);
     const size_t kk = (size_t)K * (size_t)K * sizeof(double);
     c = 0;
     g = align_up((size_t)K * (size_t)b * sizeof(float), 256);
@@ -517,7 +339,7 @@ extern "C" int flr_dnc_select(const float* X, int64_t K, int64_t P, int64_t ldx,
   double* part = reinterpret_cast<double*>(ws + lay.part);
   int32_t* bad_all = reinterpret_cast<int32_t*>(ws + lay.bad);
   int32_t* keep0 = reinterpret_cast<int32_t*>(ws + lay.keep0);
-  const dnc::GramPlan plan(K, b);
+  const rows::ColumnChunks plan = dnc::gram_chunks(K, b);
   const dim3 block(dnc::THREADS);
   const dim3 gathergrid((unsigned)((b + dnc::THREADS - 1) / dnc::THREADS),
                         (unsigned)((K + dnc::STREAM - 1) / dnc::STREAM));
@@ -539,14 +361,12 @@ extern "C" int flr_dnc_select(const float* X, int64_t K, int64_t P, int64_t ldx,
     rc = launch_status("dnc center");
     if (rc != FLR_OK) return rc;
     hipLaunchKernelGGL(dnc::gram_kernel, dim3(gt, gt, (unsigned)plan.splits), dim3(dnc::GT * dnc::GT), 0, st, C,
-                       (int)K, (int)b, plan.chunk, plan.splits > 1 ? part : G);
+                       (int)K, (int)b, (int)plan.chunk, plan.splits > 1 ? part : G);
     rc = launch_status("dnc gram");
     if (rc != FLR_OK) return rc;
     if (plan.splits > 1) {
-      const int n = (int)(K * K);
-      hipLaunchKernelGGL(dnc::gram_reduce_kernel, dim3((unsigned)((n + dnc::THREADS - 1) / dnc::THREADS)), block, 0,
-                         st, part, plan.splits, n, G);
-      rc = launch_status("dnc gram reduce");
+      // the partial matrices are symmetric bit for bit (gram_kernel): the one sum per pair is both entries
+      rc = rows::gram_reduce(part, plan.splits, (int)K, G, st);
       if (rc != FLR_OK) return rc;
     }
     if (reg)
@@ -561,22 +381,4 @@ extern "C" int flr_dnc_select(const float* X, int64_t K, int64_t P, int64_t ldx,
     if (rc != FLR_OK) return rc;
   }
   return FLR_OK;
-}
-
-extern "C" int flr_rows_mean_keep(const float* X, int64_t K, int64_t P, int64_t ldx, const int32_t* keep, float* out,
-                                  void* stream) {
-  if (!X || !keep || !out || K < 1 || P < 0 || ldx < P) return FLR_ERR_ARG;
-  if (K > dnc::KEEP_MAXROWS) return FLR_ERR_UNSUPPORTED;
-  if (P == 0) return FLR_OK;
-  const bool vec = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 && ldx % 4 == 0;
-  const int64_t lanes = vec ? P / 4 + (P & 3) : P;
-  int64_t nblocks = (lanes + dnc::THREADS - 1) / dnc::THREADS;
-  if (nblocks > 256 * 16) nblocks = 256 * 16;  // flr_rows_mean's grid: the lanes stride over the rest
-  hipStream_t st = as_stream(stream);
-  const dim3 grid((unsigned)nblocks), block(dnc::THREADS);
-  if (vec)
-    hipLaunchKernelGGL(dnc::rows_mean_keep_kernel<true>, grid, block, 0, st, X, (int)K, P, ldx, keep, out);
-  else
-    hipLaunchKernelGGL(dnc::rows_mean_keep_kernel<false>, grid, block, 0, st, X, (int)K, P, ldx, keep, out);
-  return launch_status("rows_mean_keep");
 }

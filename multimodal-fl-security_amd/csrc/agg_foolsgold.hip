@@ -16,7 +16,7 @@
 //                          step without the division)
 //
 // The Gram kernel.  A workgroup of four waves owns one 64 x 64 block of G on or
-// above the diagonal over one chunk of columns (a function of K and P: GramPlan).
+// above the diagonal over one chunk of columns (a function of K and P: gram_chunks).
 // It stages 64-column fp32 tiles of the two row blocks in LDS (one on a diagonal
 // block), the next tile's global loads in flight while this one is summed; rows
 // past K and columns past P enter as zeros through guarded loads.  Wave (wr, wc)
@@ -30,88 +30,56 @@
 // The conversion fp32 -> fp64 happens between LDS and the fragment.  A wave whose
 // quarter of a diagonal block lies below the diagonal issues no MFMA.
 // One chunk: the block goes to G, every entry with i <= j also to its mirror.
-// More: to the chunk's partial matrix; reduce_kernel adds the partials in chunk
-// order and writes G_ij and G_ji from the one sum.  VEC (A, center 16-B aligned,
+// More: to the chunk's partial matrix; gram_reduce_kernel adds the partials in
+// chunk order and writes G_ij and G_ji from the one sum (DnC's Gram, agg_dnc.hip,
+// ends in the same kernel).  VEC (A, center 16-B aligned,
 // lda % 4 == 0): float4 global loads; the same values reach the same LDS cells,
 // so the same bits as the scalar path.
-#include "flr_common.h"
+#include "rows_pass.h"
 
 namespace flr {
 namespace foolsgold {
 
-constexpr int THREADS = 256;
-constexpr int STREAM = 16;          // loads in flight per lane (combine)
-constexpr int MAXK = 1024;          // the weights kernel: one lane per client
+using namespace rows;       // THREADS, STREAM (combine), the lane map, load / store (rows_pass.h)
+constexpr int MAXK = 1024;  // the weights kernel: one lane per client
 constexpr int COMBINE_MAXROWS = 4096;
-constexpr int GB = 64;              // Gram: block edge, columns per LDS tile
-constexpr int GLD = GB + 4;         // LDS row stride in floats (272 B)
-constexpr int GRAM_BLOCKS = 2048;   // the workgroups the column chunks are chosen to reach: 256 CUs x 4 resident x 2
-constexpr int GRAM_MIN_CHUNK = 4 * GB;
+constexpr int GB = 64;       // Gram: block edge, columns per LDS tile
+constexpr int GLD = GB + 4;  // LDS row stride in floats (272 B)
 constexpr int W_THREADS = 1024;
 constexpr int W_WAVES = W_THREADS / 64;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
-
-__device__ __forceinline__ float uniform(float x) {
-  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(x)));
-}
 
 // ---- flr_rows_accumulate ----
 
-// Row blockIdx.y.  VEC: lane q < P / 4 owns coordinates [4q, 4q + 4), the next
-// P % 4 lanes one coordinate of the tail each; otherwise lane q owns coordinate q.
+// Row blockIdx.y; the lanes stride over the lane map (lane_columns).
 template <bool VEC>
 __global__ __launch_bounds__(THREADS) void accumulate_kernel(float* __restrict__ H, int64_t ldh,
                                                              const float* __restrict__ X, int64_t ldx,
                                                              const float* __restrict__ c, int64_t P) {
   float* h = H + (int64_t)blockIdx.y * ldh;
   const float* x = X + (int64_t)blockIdx.y * ldx;
-  const int64_t stride = (int64_t)gridDim.x * THREADS;
-  if constexpr (VEC) {
-    const int64_t nv = P / 4, lanes = nv + (P & 3);
-    for (int64_t q = (int64_t)blockIdx.x * THREADS + threadIdx.x; q < lanes; q += stride) {
-      if (q < nv) {
-        const f32x4 hv = *reinterpret_cast<const f32x4*>(h + 4 * q);
-        const f32x4 xv = *reinterpret_cast<const f32x4*>(x + 4 * q);
-        const f32x4 cv = *reinterpret_cast<const f32x4*>(c + 4 * q);
-        f32x4 o;
+  const int64_t lanes = VEC ? P / 4 + (P & 3) : P, stride = (int64_t)gridDim.x * THREADS;
+  for (int64_t q = (int64_t)blockIdx.x * THREADS + threadIdx.x; q < lanes; q += stride)
+    lane_columns<VEC>(q, P, [&](auto w, int64_t p) {
+      constexpr int W = decltype(w)::value;
+      float hv[W], xv[W], cv[W];
+      load<W>(h + p, hv);
+      load<W>(x + p, xv);
+      load<W>(c + p, cv);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) o[e] = add_rn(hv[e], sub_rn(xv[e], cv[e]));
-        *reinterpret_cast<f32x4*>(h + 4 * q) = o;
-      } else {
-        const int64_t p = 4 * nv + (q - nv);
-        h[p] = add_rn(h[p], sub_rn(x[p], c[p]));
-      }
-    }
-  } else {
-    for (int64_t p = (int64_t)blockIdx.x * THREADS + threadIdx.x; p < P; p += stride)
-      h[p] = add_rn(h[p], sub_rn(x[p], c[p]));
-  }
+      for (int e = 0; e < W; ++e) hv[e] = add_rn(hv[e], sub_rn(xv[e], cv[e]));
+      store<W>(h + p, hv);
+    });
 }
 
 // ---- flr_rows_gram ----
 
-// The column chunks: a K x K matrix has few 64 x 64 blocks on or above the
-// diagonal (3 at K = 128), so the columns are cut into chunks of whole LDS tiles,
-// about GRAM_BLOCKS workgroups in all and at least GRAM_MIN_CHUNK columns each.
-// A function of (K, P) alone: the summation order is the same from run to run.
-struct GramPlan {
-  int64_t chunk;
-  int splits, nb, pairs;
-  GramPlan(int64_t K, int64_t P) {
-    nb = (int)((K + GB - 1) / GB);
-    pairs = nb * (nb + 1) / 2;
-    const int64_t want = GRAM_BLOCKS / pairs;
-    int64_t c = want < 1 ? P : (P + want - 1) / want;
-    c = (c + GB - 1) / GB * GB;
-    if (c < GRAM_MIN_CHUNK) c = GRAM_MIN_CHUNK;
-    chunk = c;
-    splits = (int)((P + c - 1) / c);
-  }
-};
+// The 64 x 64 blocks on or above the diagonal, and the column chunks they are
+// summed over (ColumnChunks).
+inline int gram_blocks(int64_t K) { return (int)((K + GB - 1) / GB); }
+inline int gram_pairs(int64_t K) { return gram_blocks(K) * (gram_blocks(K) + 1) / 2; }
+inline ColumnChunks gram_chunks(int64_t K, int64_t P) { return ColumnChunks(gram_pairs(K), P, GB); }
 
 // One 64 x 64-column tile of row block r0 into registers: zeros past K and past
 // pe; with a center, fl(a - center).
@@ -290,32 +258,6 @@ __global__ __launch_bounds__(THREADS) void gram_reduce_kernel(const double* __re
 
 // ---- flr_foolsgold_weights ----
 
-__device__ __forceinline__ double block_max(double v, double* red) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    const double o = __shfl_xor(v, m);
-    v = o > v ? o : v;
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = red[0];
-#pragma unroll
-  for (int w = 1; w < W_WAVES; ++w) s = red[w] > s ? red[w] : s;
-  return s;
-}
-__device__ __forceinline__ int block_or(int v, int* red) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v |= __shfl_xor(v, m);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  int s = 0;
-#pragma unroll
-  for (int w = 0; w < W_WAVES; ++w) s |= red[w];
-  return s;
-}
-
 __device__ __forceinline__ bool finite64(double x) {
   return ((uint64_t)__double_as_longlong(x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
 }
@@ -361,8 +303,8 @@ __global__ __launch_bounds__(W_THREADS) void weights_kernel(const double* __rest
     }
   }
   double w = fmin(1.0, fmax(0.0, 1.0 - mp));
-  const double top = block_max(good ? w : -1.0, red);
-  const int anybad = block_or(bad ? 1 : 0, ired);
+  const double top = block_reduce<W_WAVES>(good ? w : -1.0, red, [](double v, double o) { return o > v ? o : v; });
+  const int anybad = block_reduce<W_WAVES>(bad ? 1 : 0, ired, [](int v, int o) { return v | o; });
   double a = 0.0;
   if (good && top > 0.0) {
     if (K == 1) {
@@ -386,20 +328,9 @@ __global__ __launch_bounds__(W_THREADS) void weights_kernel(const double* __rest
 
 // ---- flr_rows_combine_from ----
 
-template <int W>
-__device__ __forceinline__ void load(const float* __restrict__ p, float (&x)[W]) {
-  if constexpr (W == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = t[e];
-  } else {
-    x[0] = *p;
-  }
-}
-
 // W adjacent coordinates from p on: the rows in groups of STREAM loads, each
 // under its wave-uniform test of beta (a rejected row is not read); a partial
-// last group tests the row index too.
+// last group tests the row index too.  Not stream_rows: its loads are unconditional.
 template <int W>
 __device__ __forceinline__ void combine_columns(const float* __restrict__ X, int K, int64_t ldx, int64_t p,
                                                 const float* __restrict__ center, const float* bs,
@@ -428,14 +359,9 @@ __device__ __forceinline__ void combine_columns(const float* __restrict__ X, int
       }
     }
   }
-  if constexpr (W == 4) {
-    f32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = add_rn(c[e], acc[e]);
-    *reinterpret_cast<f32x4*>(out + p) = o;
-  } else {
-    out[p] = add_rn(c[0], acc[0]);
-  }
+  for (int e = 0; e < W; ++e) acc[e] = add_rn(c[e], acc[e]);
+  store<W>(out + p, acc);
 }
 
 template <bool VEC>
@@ -445,21 +371,19 @@ __global__ __launch_bounds__(THREADS) void combine_kernel(const float* __restric
   __shared__ float bs[COMBINE_MAXROWS];
   for (int t = threadIdx.x; t < K; t += THREADS) bs[t] = beta[t];
   __syncthreads();
-  const int64_t q = (int64_t)blockIdx.x * THREADS + threadIdx.x;
-  if constexpr (VEC) {
-    const int64_t nv = P / 4;
-    if (q < nv) combine_columns<4>(X, K, ldx, 4 * q, center, bs, out);
-    else if (q < nv + (P & 3)) combine_columns<1>(X, K, ldx, 4 * nv + (q - nv), center, bs, out);
-  } else {
-    if (q < P) combine_columns<1>(X, K, ldx, q, center, bs, out);
-  }
-}
-
-inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr) {
-  return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+  lane_columns<VEC>((int64_t)blockIdx.x * THREADS + threadIdx.x, P, [&](auto w, int64_t p) {
+    combine_columns<decltype(w)::value>(X, K, ldx, p, center, bs, out);
+  });
 }
 
 }  // namespace foolsgold
+
+int rows::gram_reduce(const double* part, int splits, int K, double* G, hipStream_t st) {
+  hipLaunchKernelGGL(foolsgold::gram_reduce_kernel, dim3((unsigned)((K * K + THREADS - 1) / THREADS)), dim3(THREADS), 0,
+                     st, part, splits, K, G);
+  return launch_status("gram reduce");
+}
+
 }  // namespace flr
 
 using namespace flr;
@@ -468,9 +392,8 @@ extern "C" int flr_rows_accumulate(float* H, int64_t ldh, const float* X, int64_
                                    int64_t P, void* stream) {
   if (!H || !X || !center || K < 1 || P < 1 || ldh < P || ldx < P || H == X) return FLR_ERR_ARG;
   if (K > 65535) return FLR_ERR_UNSUPPORTED;
-  const bool vec = foolsgold::aligned16(H, X, center) && ldh % 4 == 0 && ldx % 4 == 0;
-  const int64_t lanes = vec ? P / 4 + (P & 3) : P;
-  int64_t nblocks = (lanes + foolsgold::THREADS - 1) / foolsgold::THREADS;
+  const bool vec = rows::vec_ok(H, X, center, ldh, ldx);
+  int64_t nblocks = (rows::column_lanes(vec, P) + foolsgold::THREADS - 1) / foolsgold::THREADS;
   if (nblocks > 65536) nblocks = 65536;  // the lanes stride over the rest
   const dim3 grid((unsigned)nblocks, (unsigned)K), block(foolsgold::THREADS);
   hipStream_t st = as_stream(stream);
@@ -482,7 +405,7 @@ extern "C" int flr_rows_accumulate(float* H, int64_t ldh, const float* X, int64_
 }
 
 extern "C" int64_t flr_rows_gram_splits(int64_t K, int64_t P) {
-  return (K < 1 || P < 1 || K > foolsgold::MAXK) ? 0 : foolsgold::GramPlan(K, P).splits;
+  return (K < 1 || P < 1 || K > foolsgold::MAXK) ? 0 : foolsgold::gram_chunks(K, P).splits;
 }
 
 extern "C" size_t flr_rows_gram_workspace(int64_t K, int64_t P) {
@@ -494,27 +417,24 @@ extern "C" int flr_rows_gram(const float* A, int64_t K, int64_t P, int64_t lda, 
                              void* workspace, size_t workspace_bytes, void* stream) {
   if (!A || !G || K < 1 || P < 1 || lda < P) return FLR_ERR_ARG;
   if (K > foolsgold::MAXK) return FLR_ERR_UNSUPPORTED;
-  const foolsgold::GramPlan plan(K, P);
+  const rows::ColumnChunks plan = foolsgold::gram_chunks(K, P);
   if (plan.splits > 1 && (!workspace || workspace_bytes < flr_rows_gram_workspace(K, P) ||
                           (reinterpret_cast<uintptr_t>(workspace) & 255) != 0))
     return FLR_ERR_WORKSPACE;
   hipStream_t st = as_stream(stream);
-  const bool vec = foolsgold::aligned16(A, center) && lda % 4 == 0;
+  const bool vec = rows::vec_ok(A, center, lda);
   const int mirror = plan.splits == 1 ? 1 : 0;
   double* dst = mirror ? G : static_cast<double*>(workspace);
-  const dim3 grid((unsigned)plan.pairs, (unsigned)plan.splits), block(foolsgold::THREADS);
+  const dim3 grid((unsigned)foolsgold::gram_pairs(K), (unsigned)plan.splits), block(foolsgold::THREADS);
   if (vec)
     hipLaunchKernelGGL(foolsgold::gram_kernel<true>, grid, block, 0, st, A, (int)K, P, lda, center, plan.chunk,
-                       plan.nb, mirror, dst);
+                       foolsgold::gram_blocks(K), mirror, dst);
   else
     hipLaunchKernelGGL(foolsgold::gram_kernel<false>, grid, block, 0, st, A, (int)K, P, lda, center, plan.chunk,
-                       plan.nb, mirror, dst);
+                       foolsgold::gram_blocks(K), mirror, dst);
   int rc = launch_status("rows_gram");
   if (rc != FLR_OK || mirror) return rc;
-  const int n = (int)(K * K);
-  hipLaunchKernelGGL(foolsgold::gram_reduce_kernel, dim3((unsigned)((n + foolsgold::THREADS - 1) / foolsgold::THREADS)),
-                     dim3(foolsgold::THREADS), 0, st, static_cast<const double*>(workspace), plan.splits, (int)K, G);
-  return launch_status("rows_gram reduce");
+  return rows::gram_reduce(static_cast<const double*>(workspace), plan.splits, (int)K, G, st);
 }
 
 extern "C" int flr_foolsgold_weights(const double* G, int64_t K, double kappa, double* alpha, float* beta,
@@ -530,9 +450,8 @@ extern "C" int flr_rows_combine_from(const float* X, int64_t K, int64_t P, int64
                                      const float* beta, float* out, void* stream) {
   if (!X || !center || !beta || !out || K < 1 || P < 1 || ldx < P || out == center) return FLR_ERR_ARG;
   if (K > foolsgold::COMBINE_MAXROWS) return FLR_ERR_UNSUPPORTED;
-  const bool vec = foolsgold::aligned16(X, center, out) && ldx % 4 == 0;
-  const int64_t lanes = vec ? P / 4 + (P & 3) : P;
-  const int64_t nblocks = (lanes + foolsgold::THREADS - 1) / foolsgold::THREADS;
+  const bool vec = rows::vec_ok(X, center, out, ldx);
+  const int64_t nblocks = (rows::column_lanes(vec, P) + foolsgold::THREADS - 1) / foolsgold::THREADS;
   if (nblocks > 0x7fffffffLL) return FLR_ERR_UNSUPPORTED;
   const dim3 grid((unsigned)nblocks), block(foolsgold::THREADS);
   hipStream_t st = as_stream(stream);

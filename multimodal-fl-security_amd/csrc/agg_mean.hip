@@ -9,17 +9,23 @@
 //     sum(n_i * u_i for i in clients) / total                 # fp32 mul, add, div
 // Python's sum() starts from int 0, so the first add is 0 + u0 (turns -0 into
 // +0); that is kept.  Every op is a separately rounded fp32 op (no FMA).
-#include "flr_common.h"
+//
+// flr_rows_mean_keep (DnC's aggregate, agg_dnc.hip) is the same mean over the rows
+// with keep != 0: their ascending list is compacted into LDS by one wave (ballot +
+// popcount), then the sum with 16 loads in flight per lane — only kept rows are
+// read.
+//
+// The grid-stride loop, its scalar tail and the sum itself are rows_pass.h's
+// column_sum; each kernel here is its LDS set-up and one call.
+#include "rows_pass.h"
 
 #include <algorithm>
 
 namespace flr {
 namespace mean {
 
-constexpr int THREADS = 256;
+using namespace rows;  // THREADS, grid_for, vec_ok, column_sum, stream_rows (rows_pass.h)
 constexpr int MAXROWS = 4096;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <bool VEC>
 __global__ __launch_bounds__(THREADS) void rows_mean_kernel(const float* __restrict__ X, int64_t P,
@@ -30,33 +36,7 @@ __global__ __launch_bounds__(THREADS) void rows_mean_kernel(const float* __restr
   // an index outside [0, K) is clamped into range: no out-of-bounds read (flr.h)
   for (int t = threadIdx.x; t < m; t += THREADS) rs[t] = (int32_t)min((uint32_t)rows[t], rmax);
   __syncthreads();
-  if constexpr (VEC) {
-    const int64_t nv = P / 4;
-    for (int64_t v = (int64_t)blockIdx.x * THREADS + threadIdx.x; v < nv; v += (int64_t)gridDim.x * THREADS) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      for (int t = 0; t < m; ++t) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(X + (int64_t)rs[t] * ldx + 4 * v);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] = add_rn(acc[e], x[e]);
-      }
-      f32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = div_rn(acc[e], fm);
-      *reinterpret_cast<f32x4*>(out + 4 * v) = o;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (P & 3)) {  // scalar tail
-      const int64_t p = nv * 4 + threadIdx.x;
-      float acc = 0.f;
-      for (int t = 0; t < m; ++t) acc = add_rn(acc, X[(int64_t)rs[t] * ldx + p]);
-      out[p] = div_rn(acc, fm);
-    }
-  } else {
-    for (int64_t p = (int64_t)blockIdx.x * THREADS + threadIdx.x; p < P; p += (int64_t)gridDim.x * THREADS) {
-      float acc = 0.f;
-      for (int t = 0; t < m; ++t) acc = add_rn(acc, X[(int64_t)rs[t] * ldx + p]);
-      out[p] = div_rn(acc, fm);
-    }
-  }
+  column_sum<VEC>(X, P, ldx, m, [&](int t) { return rs[t]; }, [](int, float x) { return x; }, fm, out);
 }
 
 template <bool VEC>
@@ -72,35 +52,8 @@ __global__ __launch_bounds__(THREADS) void fedavg_kernel(const float* __restrict
     total_f = (float)tot;
   }
   __syncthreads();
-  const float tf = total_f;
-  if constexpr (VEC) {
-    const int64_t nv = P / 4;
-    for (int64_t v = (int64_t)blockIdx.x * THREADS + threadIdx.x; v < nv; v += (int64_t)gridDim.x * THREADS) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      for (int i = 0; i < K; ++i) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(X + (int64_t)i * ldx + 4 * v);
-        const float w = wts[i];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] = add_rn(acc[e], mul_rn(w, x[e]));
-      }
-      f32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = div_rn(acc[e], tf);
-      *reinterpret_cast<f32x4*>(out + 4 * v) = o;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (P & 3)) {  // scalar tail
-      const int64_t p = nv * 4 + threadIdx.x;
-      float acc = 0.f;
-      for (int i = 0; i < K; ++i) acc = add_rn(acc, mul_rn(wts[i], X[(int64_t)i * ldx + p]));
-      out[p] = div_rn(acc, tf);
-    }
-  } else {
-    for (int64_t p = (int64_t)blockIdx.x * THREADS + threadIdx.x; p < P; p += (int64_t)gridDim.x * THREADS) {
-      float acc = 0.f;
-      for (int i = 0; i < K; ++i) acc = add_rn(acc, mul_rn(wts[i], X[(int64_t)i * ldx + p]));
-      out[p] = div_rn(acc, tf);
-    }
-  }
+  column_sum<VEC>(X, P, ldx, K, [](int i) { return i; }, [&](int i, float x) { return mul_rn(wts[i], x); }, total_f,
+                  out);
 }
 
 // rows_mean over a matrix whose dead-tap ranges are not written (the round
@@ -121,28 +74,13 @@ __global__ __launch_bounds__(THREADS) void rows_mean_live_kernel(const float* __
   __shared__ int32_t rs[MAXROWS];
   for (int t = threadIdx.x; t < m; t += THREADS) rs[t] = (int32_t)min((uint32_t)rows[t], rmax);
   __syncthreads();
-  const int64_t nv = P / 4;
-  for (int64_t v = (int64_t)blockIdx.x * THREADS + threadIdx.x; v < nv; v += (int64_t)gridDim.x * THREADS) {
-    bool skip = false;
-    for (int r = 0; r < dr.n; ++r) skip |= 4 * v >= dr.off[r] && 4 * v + 4 <= dr.end[r];
-    if (skip) continue;
-    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int t = 0; t < m; ++t) {
-      const f32x4 x = *reinterpret_cast<const f32x4*>(X + (int64_t)rs[t] * ldx + 4 * v);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[e] = add_rn(acc[e], x[e]);
-    }
-    f32x4 o;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = div_rn(acc[e], fm);
-    *reinterpret_cast<f32x4*>(out + 4 * v) = o;
-  }
-  if (blockIdx.x == 0 && threadIdx.x < (P & 3)) {  // scalar tail (a dead tail is rewritten below)
-    const int64_t p = nv * 4 + threadIdx.x;
-    float acc = 0.f;
-    for (int t = 0; t < m; ++t) acc = add_rn(acc, X[(int64_t)rs[t] * ldx + p]);
-    out[p] = div_rn(acc, fm);
-  }
+  // a dead scalar tail is summed all the same and rewritten by dead_mean_kernel
+  column_sum<true>(X, P, ldx, m, [&](int t) { return rs[t]; }, [](int, float x) { return x; }, fm, out,
+                   [&](int64_t p) {
+                     bool skip = false;
+                     for (int r = 0; r < dr.n; ++r) skip |= p >= dr.off[r] && p + 4 <= dr.end[r];
+                     return skip;
+                   });
 }
 // grid (slices, ranges): out[p] of dead range r from gdead[p] and the rows' signs
 __global__ __launch_bounds__(THREADS) void dead_mean_kernel(const float* __restrict__ g,
@@ -162,14 +100,52 @@ __global__ __launch_bounds__(THREADS) void dead_mean_kernel(const float* __restr
   }
 }
 
-inline int grid_for(int64_t work) {
-  int64_t g = (work + THREADS - 1) / THREADS;
-  if (g > 256 * 16) g = 256 * 16;
-  return (int)(g < 1 ? 1 : g);
+// W adjacent coordinates from p on: the m listed rows streamed (stream_rows), a
+// row index one wave-uniform value.  m == 0: 0 / 0.
+template <int W>
+__device__ __forceinline__ void mean_columns(const float* __restrict__ X, int64_t ldx, int64_t p, const int32_t* rs,
+                                             int m, float fm, float* __restrict__ out) {
+  float acc[W];
+#pragma unroll
+  for (int e = 0; e < W; ++e) acc[e] = 0.f;
+  stream_rows<W>(X + p, ldx, m, [&](int t) { return __builtin_amdgcn_readfirstlane(rs[t]); },
+                 [&](int, const float(&x)[W]) {
+#pragma unroll
+                   for (int e = 0; e < W; ++e) acc[e] = add_rn(acc[e], x[e]);
+                 });
+#pragma unroll
+  for (int e = 0; e < W; ++e) acc[e] = div_rn(acc[e], fm);
+  store<W>(out + p, acc);
 }
 
-inline bool vec_ok(const void* X, int64_t ldx, int64_t P, const void* out) {
-  return ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 && ldx % 4 == 0;
+// The mean of the rows with keep != 0.  Wave 0 compacts their indices, ascending,
+// into LDS (ballot + popcount per 64 rows): the row loop reads kept rows only, a
+// wave-uniform index per load.  The lanes stride over the lane map (lane_columns).
+// Streamed, where rows_mean_kernel's loop is plain: at a small m the stream
+// re-reads the last row up to 15 times, so the two are not one kernel.
+template <bool VEC>
+__global__ __launch_bounds__(THREADS) void rows_mean_keep_kernel(const float* __restrict__ X, int K, int64_t P,
+                                                                 int64_t ldx, const int32_t* __restrict__ keep,
+                                                                 float* __restrict__ out) {
+  __shared__ int32_t rs[MAXROWS];
+  __shared__ int m_s;
+  if (threadIdx.x < 64) {
+    int base = 0;
+    for (int i0 = 0; i0 < K; i0 += 64) {
+      const int i = i0 + (int)threadIdx.x;
+      const bool k = i < K && keep[i] != 0;
+      const unsigned long long mask = __ballot(k);
+      if (k) rs[base + __popcll(mask & ((1ull << threadIdx.x) - 1ull))] = i;
+      base += __popcll(mask);
+    }
+    if (threadIdx.x == 0) m_s = base;
+  }
+  __syncthreads();
+  const int m = m_s;
+  const float fm = (float)m;
+  const int64_t lanes = VEC ? P / 4 + (P & 3) : P, stride = (int64_t)gridDim.x * THREADS;
+  for (int64_t q = (int64_t)blockIdx.x * THREADS + threadIdx.x; q < lanes; q += stride)
+    lane_columns<VEC>(q, P, [&](auto w, int64_t p) { mean_columns<decltype(w)::value>(X, ldx, p, rs, m, fm, out); });
 }
 
 }  // namespace mean
@@ -184,7 +160,7 @@ extern "C" int flr_rows_mean(const float* X, int64_t K, int64_t P, int64_t ldx, 
   if (m > mean::MAXROWS) return FLR_ERR_UNSUPPORTED;
   if (P == 0) return FLR_OK;
   hipStream_t st = as_stream(stream);
-  if (mean::vec_ok(X, ldx, P, out)) {
+  if (mean::vec_ok(X, out, ldx)) {
     hipLaunchKernelGGL(mean::rows_mean_kernel<true>, dim3(mean::grid_for(P / 4)), dim3(mean::THREADS), 0, st,
                        X, P, ldx, rows, (int)m, fdiv, out, (uint32_t)(K - 1));
   } else {
@@ -211,7 +187,7 @@ extern "C" int flr_rows_mean_dead(const float* X, int64_t K, int64_t P, int64_t 
     longest = std::max(longest, dead_n[r]);
   }
   if (P == 0) return FLR_OK;
-  if (!mean::vec_ok(X, ldx, P, out)) return FLR_ERR_ARG;  // the engine's matrix: 16-B rows
+  if (!mean::vec_ok(X, out, ldx)) return FLR_ERR_ARG;  // the engine's matrix: 16-B rows
   hipStream_t st = as_stream(stream);
   const float fdiv = (float)divisor;
   hipLaunchKernelGGL(mean::rows_mean_live_kernel, dim3(mean::grid_for(P / 4)), dim3(mean::THREADS), 0, st, X, P, ldx,
@@ -230,7 +206,7 @@ extern "C" int flr_fedavg(const float* X, int64_t K, int64_t P, int64_t ldx, con
   if (K > mean::MAXROWS) return FLR_ERR_UNSUPPORTED;
   if (P == 0) return FLR_OK;
   hipStream_t st = as_stream(stream);
-  if (mean::vec_ok(X, ldx, P, out)) {
+  if (mean::vec_ok(X, out, ldx)) {
     hipLaunchKernelGGL(mean::fedavg_kernel<true>, dim3(mean::grid_for(P / 4)), dim3(mean::THREADS), 0, st, X,
                        (int)K, P, ldx, num_examples, out);
   } else {
@@ -238,4 +214,19 @@ extern "C" int flr_fedavg(const float* X, int64_t K, int64_t P, int64_t ldx, con
                        (int)K, P, ldx, num_examples, out);
   }
   return launch_status("fedavg_kernel");
+}
+
+extern "C" int flr_rows_mean_keep(const float* X, int64_t K, int64_t P, int64_t ldx, const int32_t* keep, float* out,
+                                  void* stream) {
+  if (!X || !keep || !out || K < 1 || P < 0 || ldx < P) return FLR_ERR_ARG;
+  if (K > mean::MAXROWS) return FLR_ERR_UNSUPPORTED;
+  if (P == 0) return FLR_OK;
+  const bool vec = mean::vec_ok(X, out, ldx);
+  const dim3 grid(mean::grid_for(mean::column_lanes(vec, P))), block(mean::THREADS);
+  hipStream_t st = as_stream(stream);
+  if (vec)
+    hipLaunchKernelGGL(mean::rows_mean_keep_kernel<true>, grid, block, 0, st, X, (int)K, P, ldx, keep, out);
+  else
+    hipLaunchKernelGGL(mean::rows_mean_keep_kernel<false>, grid, block, 0, st, X, (int)K, P, ldx, keep, out);
+  return launch_status("rows_mean_keep");
 }

@@ -22,16 +22,14 @@
 //
 // flr_weighted_rows: out = (sum_j fl(fl(X[r_j] * s_j) * w_j)) / divisor,
 // sequential in j from +0 (Python sum() order, each op rounded separately).
-#include "flr_common.h"
+#include "rows_pass.h"
 
 namespace flr {
 namespace norm {
 
-constexpr int THREADS = 256;
+using namespace rows;     // THREADS, f32x4, grid_for, vec_ok, column_sum (rows_pass.h)
 constexpr int NBLK = 64;  // partial blocks per row
 constexpr int MAXROWS = 4096;
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 template <int TYPE, bool CENTER, bool VEC>
 __global__ __launch_bounds__(THREADS) void partial_kernel(const float* __restrict__ X, int64_t P, int64_t ldx,
@@ -102,43 +100,10 @@ __global__ __launch_bounds__(THREADS) void weighted_rows_kernel(const float* __r
     if constexpr (SCALE) ss[t] = s[t];
   }
   __syncthreads();
-  auto term = [&](int t, float x) {
+  column_sum<VEC>(X, P, ldx, m, [&](int t) { return rs[t]; }, [&](int t, float x) {
     if constexpr (SCALE) x = mul_rn(x, ss[t]);
     return mul_rn(x, ws[t]);
-  };
-  if constexpr (VEC) {
-    const int64_t nv = P / 4;
-    for (int64_t q = (int64_t)blockIdx.x * THREADS + threadIdx.x; q < nv; q += (int64_t)gridDim.x * THREADS) {
-      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-      for (int t = 0; t < m; ++t) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(X + (int64_t)rs[t] * ldx + 4 * q);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc[e] = add_rn(acc[e], term(t, x[e]));
-      }
-      f32x4 o;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) o[e] = div_rn(acc[e], divisor);
-      *reinterpret_cast<f32x4*>(out + 4 * q) = o;
-    }
-    if (blockIdx.x == 0 && threadIdx.x < (P & 3)) {
-      const int64_t p = nv * 4 + threadIdx.x;
-      float acc = 0.f;
-      for (int t = 0; t < m; ++t) acc = add_rn(acc, term(t, X[(int64_t)rs[t] * ldx + p]));
-      out[p] = div_rn(acc, divisor);
-    }
-  } else {
-    for (int64_t p = (int64_t)blockIdx.x * THREADS + threadIdx.x; p < P; p += (int64_t)gridDim.x * THREADS) {
-      float acc = 0.f;
-      for (int t = 0; t < m; ++t) acc = add_rn(acc, term(t, X[(int64_t)rs[t] * ldx + p]));
-      out[p] = div_rn(acc, divisor);
-    }
-  }
-}
-
-inline int grid_for(int64_t work) {
-  int64_t g = (work + THREADS - 1) / THREADS;
-  if (g > 256 * 16) g = 256 * 16;
-  return (int)(g < 1 ? 1 : g);
+  }, divisor, out);
 }
 
 }  // namespace norm
@@ -158,7 +123,7 @@ extern "C" int flr_row_norms(const float* X, int64_t K, int64_t P, int64_t ldx, 
   hipStream_t st = as_stream(stream);
   double* part = static_cast<double*>(ws);
   const dim3 grid(norm::NBLK, (unsigned)K);
-  const bool vec = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(center)) & 15) == 0 && ldx % 4 == 0;
+  const bool vec = norm::vec_ok(X, center, ldx);
 #define FLR_NORM_LAUNCH(T, C, V)                                                                          \
   hipLaunchKernelGGL((norm::partial_kernel<T, C, V>), grid, dim3(norm::THREADS), 0, st, X, P, ldx, center, \
                      part)
@@ -186,7 +151,7 @@ extern "C" int flr_row_dots(const float* X, int64_t K, int64_t P, int64_t ldx, c
   hipStream_t st = as_stream(stream);
   double* part = static_cast<double*>(ws);
   const dim3 grid(norm::NBLK, (unsigned)K);
-  const bool vec = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(v)) & 15) == 0 && ldx % 4 == 0;
+  const bool vec = norm::vec_ok(X, v, ldx);
   if (vec) hipLaunchKernelGGL((norm::partial_kernel<2, true, true>), grid, dim3(norm::THREADS), 0, st, X, P, ldx, v, part);
   else hipLaunchKernelGGL((norm::partial_kernel<2, true, false>), grid, dim3(norm::THREADS), 0, st, X, P, ldx, v, part);
   int rc = launch_status("row_dots partial");
@@ -202,7 +167,7 @@ extern "C" int flr_weighted_rows(const float* X, int64_t K, int64_t P, int64_t l
   if (m > norm::MAXROWS) return FLR_ERR_UNSUPPORTED;
   if (P == 0) return FLR_OK;
   hipStream_t st = as_stream(stream);
-  const bool vec = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(out)) & 15) == 0 && ldx % 4 == 0;
+  const bool vec = norm::vec_ok(X, out, ldx);
   const dim3 grid(norm::grid_for(vec ? P / 4 : P));
 #define FLR_WR_LAUNCH(R, S, V)                                                                                  \
   hipLaunchKernelGGL((norm::weighted_rows_kernel<R, S, V>), grid, dim3(norm::THREADS), 0, st, X, P, ldx, rows, \

@@ -20,18 +20,15 @@
 // keeps its column in VGPRs (template on the padded count), so the second pass
 // costs no memory traffic.  Past that, and whenever sigma is not wanted at all
 // (IPM with no std_out: a plain column sum), a streaming form walks the rows
-// with 16 loads in flight and, for sigma, walks them a second time — the same
+// with 16 loads in flight (rows_pass.h's stream_rows) and, for sigma, walks them a second time — the same
 // operations in the same order, so the same bits.
-#include "flr_common.h"
+#include "rows_pass.h"
 
 namespace flr {
 namespace collude {
 
-constexpr int THREADS = 256;
-constexpr int GROUP = 8;    // rows per wave-uniform load group of the register form
-constexpr int STREAM = 16;  // loads in flight per lane in the streaming form
-
-__device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
+using rows::THREADS;
+constexpr int GROUP = 8;  // rows per wave-uniform load group of the register form
 
 template <int N>
 __device__ __forceinline__ void reg_fence(float* v) {
@@ -127,35 +124,18 @@ __global__ __launch_bounds__(THREADS) void collude_stream_kernel(float* X, int64
   const int64_t p = (int64_t)blockIdx.x * THREADS + threadIdx.x;
   if (p >= P) return;
   const float* col = X + nmal * ldx + p;
-  const int64_t nfull = nb - nb % STREAM;
+  const auto row = [](int64_t k) { return k; };
   float s = 0.f;
-  for (int64_t k0 = 0; k0 < nfull; k0 += STREAM) {
-    float t[STREAM];
-#pragma unroll
-    for (int i = 0; i < STREAM; ++i) t[i] = col[(k0 + i) * ldx];
-#pragma unroll
-    for (int i = 0; i < STREAM; ++i) s = add_rn(s, t[i]);
-  }
-  for (int64_t k = nfull; k < nb; ++k) s = add_rn(s, col[k * ldx]);
+  rows::stream_rows<1>(col, ldx, nb, row, [&](int64_t, const float(&x)[1]) { s = add_rn(s, x[0]); });
   const float fnb = (float)nb;
   const float mu = div_rn(s, fnb);
   float sigma = 0.f;
   if constexpr (SIGMA) {
     float q = 0.f;
-    for (int64_t k0 = 0; k0 < nfull; k0 += STREAM) {
-      float t[STREAM];
-#pragma unroll
-      for (int i = 0; i < STREAM; ++i) t[i] = col[(k0 + i) * ldx];
-#pragma unroll
-      for (int i = 0; i < STREAM; ++i) {
-        const float d = sub_rn(t[i], mu);
-        q = add_rn(q, mul_rn(d, d));
-      }
-    }
-    for (int64_t k = nfull; k < nb; ++k) {
-      const float d = sub_rn(col[k * ldx], mu);
+    rows::stream_rows<1>(col, ldx, nb, row, [&](int64_t, const float(&x)[1]) {
+      const float d = sub_rn(x[0], mu);
       q = add_rn(q, mul_rn(d, d));
-    }
+    });
     sigma = sqrt_rn(div_rn(q, fnb));
   }
   finish(X, p, ldx, nmal, mode, param, mu, sigma, mean_out, std_out);

@@ -35,30 +35,15 @@
 //                       closed form, gamma_out / stats_out
 //   5. the rows         write_kernel: rows [0, nmal) <- mu + (float)gamma * p, one
 //                       lane per float4; a NaN gamma skips it by a uniform branch
-#include "flr_common.h"
+#include "rows_pass.h"
 
 namespace flr {
 namespace minmax {
 
-constexpr int THREADS = 256;
+using namespace rows;          // THREADS, the lane map, load / store (rows_pass.h)
 constexpr int ROWS = 16;       // rows per workgroup = row loads in flight per lane
 constexpr int MAXCB = 128;     // column blocks (partials per row)
 constexpr int MAXROWS = 1024;  // benign rows: flr_pairwise_l2's limit (the one-workgroup solve would carry 4096)
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
-
-template <int W>
-__device__ __forceinline__ void load(const float* __restrict__ p, float (&x)[W]) {
-  if constexpr (W == 4) {
-    const f32x4 t = *reinterpret_cast<const f32x4*>(p);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = t[e];
-  } else {
-    x[0] = *p;
-  }
-}
 
 // p of one coordinate; aux is sigma (FLR_PERTURB_STD) or g (the other two).
 __device__ __forceinline__ float perturb(int pert, float mu, float aux) {
@@ -97,9 +82,9 @@ __device__ __forceinline__ void accumulate(const float* __restrict__ Xb, int las
   }
 }
 
-// grid (ncb, ceil(nb / ROWS)).  The lanes: VEC, lane q < P / 4 owns coordinates
-// [4q, 4q + 4) and the next P % 4 lanes one coordinate of the tail each; otherwise
-// lane q owns coordinate q.  Column block cb owns lanes [L cb / ncb, L (cb+1) / ncb).
+// grid (ncb, ceil(nb / ROWS)).  The lanes are the lane map's (rows_pass.h), split
+// here by column block: block cb owns lanes [L cb / ncb, L (cb+1) / ncb), its
+// float4 lanes first, so the two loops below stand in for lane_columns.
 // part: [nb][ncb] partials of a, then of b (at nbp * ncb), then [ncb] of c.
 template <bool VEC>
 __global__ __launch_bounds__(THREADS) void stats_kernel(const float* __restrict__ Xb, int nb, int64_t P, int64_t ldx,
@@ -260,15 +245,9 @@ __device__ __forceinline__ void write_columns(float* __restrict__ X, int64_t ldx
   float m[W], x[W];
   load<W>(mu + p, m);
   load<W>(aux + p, x);
-  if constexpr (W == 4) {
-    f32x4 o;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) o[e] = add_rn(m[e], mul_rn(gf, perturb(pert, m[e], x[e])));
-    for (int64_t r = 0; r < nmal; ++r) *reinterpret_cast<f32x4*>(X + r * ldx + p) = o;
-  } else {
-    const float o = add_rn(m[0], mul_rn(gf, perturb(pert, m[0], x[0])));
-    for (int64_t r = 0; r < nmal; ++r) X[r * ldx + p] = o;
-  }
+  for (int e = 0; e < W; ++e) m[e] = add_rn(m[e], mul_rn(gf, perturb(pert, m[e], x[e])));
+  for (int64_t r = 0; r < nmal; ++r) store<W>(X + r * ldx + p, m);
 }
 
 // Rows [0, nmal) <- mu + (float)gamma * p; lanes as stats_kernel's.
@@ -280,14 +259,9 @@ __global__ __launch_bounds__(THREADS) void write_kernel(float* __restrict__ X, i
   const double g = *gamma;
   if (g != g) return;  // wave-uniform: the attackers' rows stay as they were
   const float gf = (float)g;
-  const int64_t q = (int64_t)blockIdx.x * THREADS + threadIdx.x;
-  if constexpr (VEC) {
-    const int64_t nv = P / 4;
-    if (q < nv) write_columns<4>(X, ldx, nmal, 4 * q, mu, aux, pert, gf);
-    else if (q < nv + (P & 3)) write_columns<1>(X, ldx, nmal, 4 * nv + (q - nv), mu, aux, pert, gf);
-  } else {
-    if (q < P) write_columns<1>(X, ldx, nmal, q, mu, aux, pert, gf);
-  }
+  lane_columns<VEC>((int64_t)blockIdx.x * THREADS + threadIdx.x, P, [&](auto w, int64_t p) {
+    write_columns<decltype(w)::value>(X, ldx, nmal, p, mu, aux, pert, gf);
+  });
 }
 
 // Column blocks: at least four 1024-coordinate steps per workgroup.
@@ -345,9 +319,8 @@ extern "C" int flr_minmax_rows(float* X, int64_t K, int64_t P, int64_t ldx, int6
   double* stats = stats_out ? stats_out : reinterpret_cast<double*>(ws + lay.stats);
   double* gamma = gamma_out ? gamma_out : reinterpret_cast<double*>(ws + lay.gamma);
   const float* aux = perturb == FLR_PERTURB_STD ? sigma : global;
-  const bool vec = ((reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(aux)) & 15) == 0 && ldx % 4 == 0;
-  const int64_t lanes = vec ? P / 4 + (P & 3) : P;
-  const int64_t wblocks = (lanes + minmax::THREADS - 1) / minmax::THREADS;
+  const bool vec = rows::vec_ok(X, aux, ldx);
+  const int64_t wblocks = (rows::column_lanes(vec, P) + minmax::THREADS - 1) / minmax::THREADS;
   if (wblocks > 0x7fffffffLL) return FLR_ERR_UNSUPPORTED;
   hipStream_t st = as_stream(stream);
   const float* Xb = X + nmal * ldx;

@@ -41,9 +41,10 @@ int launch(float* X, int64_t K, int64_t P, int64_t ldx, int64_t nmal, int mode, 
 
 __host__ __device__ constexpr int cdiv(int a, int b) { return (a + b - 1) / b; }
 
-// fp32 add/mul/div with no contraction (the reference computes each op as a
+// fp32 add/sub/mul/div with no contraction (the reference computes each op as a
 // separate rounded torch op, so FMA contraction would break bit parity).
 __device__ __forceinline__ float add_rn(float a, float b) { return __fadd_rn(a, b); }
+__device__ __forceinline__ float sub_rn(float a, float b) { return __fsub_rn(a, b); }
 __device__ __forceinline__ float mul_rn(float a, float b) { return __fmul_rn(a, b); }
 __device__ __forceinline__ float div_rn(float a, float b) { return __fdiv_rn(a, b); }
 

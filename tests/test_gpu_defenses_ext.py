@@ -152,3 +152,35 @@ def test_geometric_median_duplicate_clients(cuda):
     assert d.used_direct
     assert abs(d.num_iters - iters) <= 1, (d.num_iters, iters)
     _close(_flat(got), want)
+
+
+@pytest.mark.parametrize("sliced", [False, True])
+@pytest.mark.parametrize("K,P", [(5, 7), (33, 1027)])
+@pytest.mark.parametrize("with_scales", [False, True])
+@pytest.mark.parametrize("with_rows", [False, True])
+def test_weighted_rows_bits(cuda, with_rows, with_scales, K, P, sliced):
+    """ops.weighted_rows itself, bit for bit against flr.h's statement: per listed
+    row fl(fl(x * s) * w), added in list order from +0, one division.  Both
+    shapes have P % 4 == 3.  Not sliced: a 16-byte aligned matrix with ldx % 4
+    == 0 (float4 lanes and the three tail lanes); sliced: columns 1.. of a wider
+    matrix, a misaligned base (one lane per coordinate)."""
+    g = torch.Generator().manual_seed(100 * K + P)
+    back = torch.randn(K, P + 1, generator=g)
+    Xc = back[:, 1:] if sliced else back[:, :P]
+    Xd = back.to(cuda)
+    Xd = Xd[:, 1:] if sliced else Xd[:, :P]
+    assert Xd.stride(0) % 4 == 0 and (Xd.data_ptr() % 16 != 0) == sliced
+    rows = torch.randperm(K, generator=g)[: K - 2].tolist() if with_rows else None
+    m = len(rows) if with_rows else K
+    w = torch.rand(m, generator=g) + 0.5
+    s = torch.rand(m, generator=g) + 0.25 if with_scales else None
+    divisor = torch.tensor(float(w.sum()) * 1.37, dtype=torch.float32)
+    acc = torch.zeros(P, dtype=torch.float32)
+    for j in range(m):
+        x = Xc[rows[j] if with_rows else j]
+        if with_scales:
+            x = x * s[j]
+        acc = acc + x * w[j]
+    want = acc / divisor
+    got = ops.weighted_rows(Xd, w, divisor.item(), rows=rows, scales=s)
+    assert torch.equal(got.cpu(), want)
