@@ -608,6 +608,61 @@ int flr_rows_combine_from(const float* X, int64_t K, int64_t P, int64_t ldx,
                           const float* center, const float* beta /* device [K] */,
                           float* out, void* stream);
 
+/* ---- the robust learning rate, RLR (Ozdayi, Kantarcioglu, Gel, AAAI 2021) ----
+ * "Defending against Backdoors in Federated Learning with Robust Learning Rate":
+ * per coordinate the clients vote with the sign of their update against the
+ * round's global model g, and where fewer than theta net votes agree the
+ * server's learning rate for that coordinate is negated, so the aggregate moves
+ * away from an unopposed minority.  The rule wraps any base aggregate agg.  No
+ * reference counterpart.  Every entry enqueues on the stream and never
+ * synchronises with the host; columns [P, ldx) of X are never touched.
+ *
+ * flr_sign_vote: for every coordinate p
+ *     votes[p] = #{k : X[k][p] > g[p]} - #{k : X[k][p] < g[p]}
+ *   Comparisons only, no arithmetic on the values (no rounding or denormal
+ *   question): a NaN on either side votes 0, -0 against +0 votes 0, +-inf votes
+ *   by its sign (against an equal inf: 0).  votes: device int32 [P], an exact
+ *   integer in [-K, K], the same with 16-byte and 4-byte loads.  The K rows are
+ *   streamed with 16 loads in flight per lane.  Bytes moved: K * P * 4 + 8 * P.
+ *
+ * flr_rlr_apply: per coordinate, every operation a separately rounded fp32 op
+ * (no FMA):
+ *     d    = agg - g
+ *     pass = |votes| >= theta
+ *     out  = agg            when pass and eta == 1   (the base aggregate's bits)
+ *          = g + eta * d    when pass and eta != 1
+ *          = g - eta * d    when not pass
+ *   so a CPU loop gives the same bits.  agg, g: device fp32 [P]; votes: device
+ *   int32 [P]; out: device fp32 [P], may be agg (in place), must not be g.
+ *   flipped: optional (NULL: not written) device int64 [1], the number of
+ *   coordinates with pass false: the call zeroes it on the stream, then each
+ *   workgroup adds its count with one atomicAdd.  Bytes moved: 16 * P.
+ *
+ * flr_rlr_fedavg: the fused default, one pass over X for the vote and the FedAvg
+ * sum.  The accumulator is flr_fedavg's: weights (float)n_i, fl(n_i * x) added
+ * in client order from +0, one division by (float)sum_i n_i.  out, votes_out
+ * (optional, device int32 [P]) and flipped (optional) equal bit for bit what
+ * flr_fedavg, then flr_sign_vote, then flr_rlr_apply produce.  num_examples:
+ * device int64 [K].  One lane owns one float4 of coordinates (or one coordinate:
+ * a pointer not 16-B aligned or ldx % 4 != 0) with W float accumulators and W
+ * int counters; the rows are streamed in row order.  Bytes moved: K * P * 4 +
+ * 8 * P (+ 4 * P with votes_out).
+ *
+ * FLR_ERR_ARG: a null required pointer; K < 1; P < 0; ldx < P; theta < 0 or
+ * theta > K (flr_rlr_apply, which takes no K: theta < 0); eta not finite or
+ * <= 0; out == g.  FLR_ERR_UNSUPPORTED: K > 4096 (flr_fedavg's limit, kept for
+ * flr_sign_vote too: the composition and the fused call accept the same shapes).
+ * P == 0: FLR_OK, flipped = 0.  Nothing is written on an error. */
+int flr_sign_vote(const float* X, int64_t K, int64_t P, int64_t ldx, const float* g,
+                  int32_t* votes, void* stream);
+int flr_rlr_apply(const float* agg, const float* g, const int32_t* votes, int64_t P,
+                  int64_t theta, float eta, float* out, int64_t* flipped /* optional */,
+                  void* stream);
+int flr_rlr_fedavg(const float* X, int64_t K, int64_t P, int64_t ldx,
+                   const int64_t* num_examples, const float* g, int64_t theta, float eta,
+                   float* out, int32_t* votes_out /* optional */,
+                   int64_t* flipped /* optional */, void* stream);
+
 /* ---- a6 + a7: fused gradient clip + SGD-momentum step -----------------
  * Replaces, for every client row at once, clip_grad_norm_(params, max_norm)
  * + torch.optim.SGD(lr, momentum, weight_decay).step()

@@ -93,6 +93,11 @@ SIGNATURES = {
     "flr_foolsgold_weights": (_int, [_c_void_p, _i64, ctypes.c_double, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                      _c_void_p]),
     "flr_rows_combine_from": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "flr_sign_vote": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p]),
+    "flr_rlr_apply": (_int, [_c_void_p, _c_void_p, _c_void_p, _i64, _i64, ctypes.c_float, _c_void_p, _c_void_p,
+                             _c_void_p]),
+    "flr_rlr_fedavg": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _i64, ctypes.c_float, _c_void_p,
+                              _c_void_p, _c_void_p, _c_void_p]),
     "flr_clip_sgd_workspace": (_size_t, [_i64]),
     "flr_clip_sgd_step": (_int, [_c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i64, ctypes.c_float, ctypes.c_float,
                                  ctypes.c_float, ctypes.c_float, _int, _c_void_p, _c_void_p, _size_t, _c_void_p]),

@@ -12,13 +12,14 @@ from .fltrust import FLTrustDefense
 from .foolsgold import FoolsGoldDefense
 from .geometric_median import GeometricMedianDefense
 from .norm_based import DPSGDDefense, GradientClippingDefense, NormBoundingDefense
+from .robust_lr import RobustLRDefense
 from .trimmed_mean import MedianDefense, TrimmedMeanDefense
 
 __all__ = [
     "BaseDefense", "NoDefense", "KrumDefense", "MultiKrumDefense", "KrumTrimmedMeanDefense", "BulyanDefense",
     "TrimmedMeanDefense", "MedianDefense", "GeometricMedianDefense",
     "GradientClippingDefense", "NormBoundingDefense", "DPSGDDefense", "FLTrustDefense", "CenteredClippingDefense",
-    "DnCDefense", "FoolsGoldDefense",
+    "DnCDefense", "FoolsGoldDefense", "RobustLRDefense",
     "get_defense",
 ]
 
@@ -44,6 +45,8 @@ _DEFENSES = {
     "dnc": DnCDefense,
     # FoolsGold (RAID 2020): sybils resemble each other; weights from the clients' pairwise cosine similarity
     "foolsgold": FoolsGoldDefense,
+    # robust learning rate (AAAI 2021): a per-coordinate sign vote negates the step where too few clients agree
+    "robust_lr": RobustLRDefense,
 }
 
 

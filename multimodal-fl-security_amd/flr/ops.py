@@ -483,6 +483,78 @@ def rows_combine_from(X: torch.Tensor, center: torch.Tensor, beta: torch.Tensor,
     return out
 
 
+def _check_rlr(theta: int, eta: float, K: Optional[int]) -> Tuple[int, float]:
+    theta, eta = int(theta), float(eta)
+    if theta < 0 or (K is not None and theta > K):
+        raise ValueError(f"theta must be in [0, K{'' if K is None else f' = {K}'}], got {theta}")
+    if not 0.0 < eta < float("inf"):
+        raise ValueError(f"eta must be a finite number > 0, got {eta}")
+    return theta, eta
+
+
+def sign_vote(X: torch.Tensor, g: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The clients' per-coordinate sign vote against g (flr_sign_vote): int32 [P],
+    #{k : X[k, p] > g[p]} - #{k : X[k, p] < g[p]} — comparisons only, so a NaN
+    votes 0 and -0 against +0 votes 0.  g: float32 [P] on X's device."""
+    K, P, ldx = _check_matrix(X)
+    _check_vector(g, P, X.device, "g")
+    if out is None:
+        out = torch.empty(P, dtype=torch.int32, device=X.device)
+    else:
+        _check_vector(out, P, X.device, "out", torch.int32)
+    _capi.call("flr_sign_vote", X.data_ptr(), K, P, ldx, g.data_ptr(), out.data_ptr(), _stream(X))
+    return out
+
+
+def rlr_apply(agg: torch.Tensor, g: torch.Tensor, votes: torch.Tensor, theta: int, eta: float = 1.0,
+              out: Optional[torch.Tensor] = None, count: bool = False):
+    """The robust learning rate's step (flr_rlr_apply): per coordinate, with d =
+    agg - g, out = g + eta * d where |votes| >= theta (agg's own bits at eta == 1)
+    and g - eta * d elsewhere; every op a separately rounded fp32 op.  out may be
+    agg (in place), not g.  Returns out, or with count (out, flipped int64 [1]: the
+    coordinates whose learning rate was negated) as device tensors."""
+    if not isinstance(agg, torch.Tensor) or not agg.is_cuda:
+        raise RuntimeError("agg must be a CUDA/HIP tensor (the engine has no CPU path)")
+    P = agg.numel()
+    _check_vector(agg, P, agg.device, "agg")
+    _check_vector(g, P, agg.device, "g")
+    _check_vector(votes, P, agg.device, "votes", torch.int32)
+    theta, eta = _check_rlr(theta, eta, None)
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=agg.device)
+    else:
+        _check_vector(out, P, agg.device, "out")
+    flipped = torch.empty(1, dtype=torch.int64, device=agg.device) if count else None
+    _capi.call("flr_rlr_apply", agg.data_ptr(), g.data_ptr(), votes.data_ptr(), P, theta, eta, out.data_ptr(),
+               _ptr(flipped), _stream(agg))
+    return (out, flipped) if count else out
+
+
+def rlr_fedavg(X: torch.Tensor, num_examples, g: torch.Tensor, theta: int, eta: float = 1.0,
+               out: Optional[torch.Tensor] = None, diagnostics: bool = False):
+    """FedAvg under the robust learning rate in one pass over X (flr_rlr_fedavg):
+    the bits of fedavg, then sign_vote, then rlr_apply.  Returns out (float32 [P];
+    must not be g), or with diagnostics (out, votes int32 [P], flipped int64 [1])
+    as device tensors."""
+    K, P, ldx = _check_matrix(X)
+    n = torch.as_tensor(num_examples, dtype=torch.int64).to(X.device).contiguous()
+    if n.numel() != K:
+        raise ValueError(f"num_examples has {n.numel()} entries for {K} clients")
+    _check_vector(g, P, X.device, "g")
+    theta, eta = _check_rlr(theta, eta, K)
+    if out is None:
+        out = torch.empty(P, dtype=torch.float32, device=X.device)
+    else:
+        _check_vector(out, P, X.device, "out")
+    votes = flipped = None
+    if diagnostics:
+        votes = torch.empty(P, dtype=torch.int32, device=X.device)
+        flipped = torch.empty(1, dtype=torch.int64, device=X.device)
+    _capi.call("flr_rlr_fedavg", X.data_ptr(), K, P, ldx, n.data_ptr(), g.data_ptr(), theta, eta, out.data_ptr(),
+               _ptr(votes), _ptr(flipped), _stream(X))
+    return (out, votes, flipped) if diagnostics else out
+
+
 def row_norms(X: torch.Tensor, center: Optional[torch.Tensor] = None, kind: str = "l2") -> torch.Tensor:
     """float64 [K]: ||X_i - center|| per row (l2 or linf); fp32 differences,
     fp64 accumulation in a fixed order (differential_privacy.py:223-236,

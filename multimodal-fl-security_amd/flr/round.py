@@ -134,6 +134,8 @@ class RoundEngine:
             cfg.setdefault("multi_k", max(1, K // 2))
         elif rcfg.defense == "dnc":
             cfg.setdefault("num_malicious", rcfg.num_attackers)
+        elif rcfg.defense == "robust_lr":  # the paper's guidance: the threshold exceeds the attacker count
+            cfg.setdefault("threshold", min(K, rcfg.num_attackers + 1))
         self.defense = get_defense(rcfg.defense, cfg)
         mode = rcfg.exchange
         if mode == "auto":
@@ -160,6 +162,8 @@ class RoundEngine:
         self._graph = None
         self._graph_losses: Optional[torch.Tensor] = None
         self._wants_global = "global_flat" in inspect.signature(self.defense.aggregate_flat).parameters
+        # the same for a rank's coordinate range: the defense takes the global model's slice
+        self._shard_wants_global = "global_flat" in inspect.signature(self.defense.aggregate_sharded).parameters
         # training-order rounds (BaseDefense.order_free): the client matrix is in
         # the trainer's coordinate order, written by the last optimizer step;
         # gtrain is the global model in that order (FLR_ORDER=torch: off)
@@ -373,6 +377,8 @@ class RoundEngine:
         if self.exchange == "alltoall":
             cs = self._slice = self.xchg.exchange(self.trainer.X.data)
             self._apply_collusion(cs.X)  # coordinate-wise: this rank's slice needs no other
+            if self._shard_wants_global:  # the robust learning rate: global_flat is overwritten below
+                kw["global_flat"] = self.global_flat[cs.begin:cs.end].clone()
             try:
                 part = self.defense.aggregate_sharded(cs, self.num_examples, **kw)
             except Exception as e:  # noqa: BLE001 - the reference catches any exception
