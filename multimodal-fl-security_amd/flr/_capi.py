@@ -10,6 +10,8 @@ import ctypes
 import os
 import threading
 
+import torch  # before the library loads: its libamdhip64.so.7 is the runtime this library binds to
+
 _PKG_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIB_PATH = os.environ.get("FLR_LIB", os.path.join(_PKG_ROOT, "lib", "libflr.so"))
 HEADER_PATH = os.path.join(os.path.dirname(_PKG_ROOT), "include", "flr.h")
@@ -247,9 +249,7 @@ def lib() -> ctypes.CDLL:
                 f"flr native library not found at {LIB_PATH}; build it with "
                 "`python -c 'import __graft_entry__ as g; g.build()'` (or make -C "
                 "multimodal-fl-security_amd/csrc). There is no CPU fallback.")
-        # torch must be imported first so its libamdhip64.so.7 is the runtime
-        # this library binds to (same SONAME -> one HIP runtime per process).
-        import torch  # noqa: F401
+        # torch is loaded (the import above): same SONAME -> one HIP runtime per process
         handle = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
         for name, (res, args) in SIGNATURES.items():
             fn = getattr(handle, name)
@@ -283,6 +283,16 @@ def check(fn: str, status: int) -> None:
         if status == FLR_ERR_HIP:
             detail = lib().flr_last_error().decode()
         raise FlrError(fn, status, detail)
+
+
+def stream_of(t) -> int:
+    """The raw handle of torch's current stream on the device tensor t's device."""
+    return torch.cuda.current_stream(t.device).cuda_stream
+
+
+def ptr(t):
+    """t's device address; None (a NULL argument) for None."""
+    return None if t is None else t.data_ptr()
 
 
 def call(fn: str, *args) -> int:

@@ -3,7 +3,7 @@
 Every name of the reference factory is registered and runs on the HIP kernels
 (FLTrust's server update runs on the client-batched trainer).
 """
-from .base_defense import BaseDefense, NoDefense
+from .base_defense import BaseDefense, CenteredDefense, NoDefense
 from .bulyan import BulyanDefense
 from .centered_clipping import CenteredClippingDefense
 from .dnc import DnCDefense
@@ -16,7 +16,7 @@ from .robust_lr import RobustLRDefense
 from .trimmed_mean import MedianDefense, TrimmedMeanDefense
 
 __all__ = [
-    "BaseDefense", "NoDefense", "KrumDefense", "MultiKrumDefense", "KrumTrimmedMeanDefense", "BulyanDefense",
+    "BaseDefense", "CenteredDefense", "NoDefense", "KrumDefense", "MultiKrumDefense", "KrumTrimmedMeanDefense", "BulyanDefense",
     "TrimmedMeanDefense", "MedianDefense", "GeometricMedianDefense",
     "GradientClippingDefense", "NormBoundingDefense", "DPSGDDefense", "FLTrustDefense", "CenteredClippingDefense",
     "DnCDefense", "FoolsGoldDefense", "RobustLRDefense",

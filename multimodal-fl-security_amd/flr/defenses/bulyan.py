@@ -13,13 +13,12 @@ tests/bulyan_ref.py restates the two stages from the oracle's Krum scores.
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List
+from typing import Any, Dict
 
 import torch
 
 from .. import ops
-from ..matrix import ClientMatrix
-from .base_defense import Updates, as_matrix, source_device
+from .base_defense import BaseDefense
 from .krum import KrumDefense
 
 MAX_ROWS = 128  # rows the window-mean kernel sorts in one lane's registers (include/flr.h)
@@ -56,33 +55,9 @@ class BulyanDefense(KrumDefense):
         self.scores_device, self.order_device = ops.krum_select_iter(self.distances, self.num_malicious, self.theta)
         return self.order_device
 
-    def select(self, cm: ClientMatrix) -> torch.Tensor:
-        self._sizes(cm.K)
-        ref = self.pairwise_method == "reference"
-        self.distances = ops.pairwise_l2(cm.X, self.pairwise_method, comm=self.comm,
-                                         tap_blocks=self.tap_blocks if ref else None)
-        self._check_refine_capacity(cm.K)
-        return self._pick()
-
-    def _combine(self, X: torch.Tensor, picked: torch.Tensor) -> torch.Tensor:
-        return ops.median_window_mean(X, self.beta, rows=picked[: self.theta])
-
-    def aggregate_flat(self, cm: ClientMatrix, num_examples: List[int], publish: bool = True) -> torch.Tensor:
-        picked = self.select(cm)
-        if publish:
-            self.publish()
-        return self._combine(cm.X, picked)
-
-    def aggregate_sharded(self, cs, num_examples: List[int], publish: bool = True, events=None) -> torch.Tensor:
-        """Sharded distances, the selection replicated on every rank, then the
-        window mean of this rank's coordinate range."""
-        self._sizes(cs.K)
-        self.distances = self._sharded_distances(cs, events)
-        self._check_refine_capacity(cs.K)
-        self._pick()
-        if publish:
-            self.publish()
-        return self._combine(cs.X, self.order_device)
+    def _combine(self, src, picked: torch.Tensor) -> torch.Tensor:
+        """The window mean of src's columns (a rank's coordinate range, or all)."""
+        return ops.median_window_mean(src.X, self.beta, rows=picked[: self.theta])
 
     def publish(self) -> None:
         picked = self.order_device.cpu().tolist()
@@ -90,11 +65,8 @@ class BulyanDefense(KrumDefense):
         self.selected_clients = picked[: self.theta]
         self.rejected_clients = picked[self.theta:]
 
-    def aggregate(self, client_updates: Updates, num_examples: List[int]) -> List[torch.Tensor]:
-        # the size rules first: a list input is not even copied to the device
-        self._sizes(client_updates.K if isinstance(client_updates, ClientMatrix) else len(client_updates))
-        cm = as_matrix(client_updates)
-        return cm.unflatten(self.aggregate_flat(cm, num_examples), source_device(client_updates))
+    _check_clients = _sizes  # for aggregate(): before a list input is copied to the device
+    aggregate = BaseDefense.aggregate  # multi_k is ignored: no single-Krum shortcut
 
     def get_metrics(self) -> Dict[str, Any]:
         m = super().get_metrics()

@@ -22,13 +22,13 @@ diagnostics stay on the device until they are asked for.
 from __future__ import annotations
 
 import math
-import numbers
 from typing import Any, Dict, List, Optional
 
 import torch
 
 from .. import ops
 from ..matrix import ClientMatrix
+from ._config import int_in, real_in
 from .base_defense import BaseDefense, Updates
 
 DEFAULT_FILTER_FRAC = 1.0
@@ -37,13 +37,6 @@ DEFAULT_SUBSAMPLE_DIM = 10000
 DEFAULT_POWER_ITERS = 32
 MAX_CLIENTS = 1024       # flr_dnc_select: one lane per client in the spectral workgroup
 MAX_SUBSAMPLE_DIM = 65536
-
-
-def _int_in(cfg: Dict[str, Any], key: str, default: int, lo: int, hi: Optional[int] = None) -> int:
-    v = cfg.get(key, default)
-    if isinstance(v, bool) or not isinstance(v, numbers.Integral) or v < lo or (hi is not None and v > hi):
-        raise ValueError(f"{key} must be an integer in [{lo}, {'inf' if hi is None else hi}], got {v!r}")
-    return int(v)
 
 
 class DnCDefense(BaseDefense):
@@ -69,15 +62,12 @@ class DnCDefense(BaseDefense):
     def __init__(self, defense_config: Dict[str, Any]):
         super().__init__(defense_config)
         cfg = defense_config
-        self.num_malicious = _int_in(cfg, "num_malicious", 0, 0)
-        c = cfg.get("filter_frac", DEFAULT_FILTER_FRAC)
-        if isinstance(c, bool) or not isinstance(c, numbers.Real) or math.isnan(c) or math.isinf(c) or c < 0:
-            raise ValueError(f"filter_frac must be a finite number >= 0, got {c!r}")
-        self.filter_frac = float(c)
-        self.niters = _int_in(cfg, "niters", DEFAULT_NITERS, 1, ops.DNC_MAX_ITERS)
-        self.subsample_dim = _int_in(cfg, "subsample_dim", DEFAULT_SUBSAMPLE_DIM, 1, MAX_SUBSAMPLE_DIM)
-        self.power_iters = _int_in(cfg, "power_iters", DEFAULT_POWER_ITERS, 1, ops.DNC_MAX_POWER_ITERS)
-        self.seed = _int_in(cfg, "seed", 0, -(1 << 63), (1 << 64) - 1)
+        self.num_malicious = int_in(cfg, "num_malicious", 0, 0)
+        self.filter_frac = real_in(cfg, "filter_frac", DEFAULT_FILTER_FRAC, 0.0, closed=True)
+        self.niters = int_in(cfg, "niters", DEFAULT_NITERS, 1, ops.DNC_MAX_ITERS)
+        self.subsample_dim = int_in(cfg, "subsample_dim", DEFAULT_SUBSAMPLE_DIM, 1, MAX_SUBSAMPLE_DIM)
+        self.power_iters = int_in(cfg, "power_iters", DEFAULT_POWER_ITERS, 1, ops.DNC_MAX_POWER_ITERS)
+        self.seed = int_in(cfg, "seed", 0, -(1 << 63), (1 << 64) - 1)
         self.calls = 0
         self.nremove = 0
         # device results of the last call
@@ -105,10 +95,8 @@ class DnCDefense(BaseDefense):
         self._published = False
         return ops.rows_mean_keep(cm.X, self._keep)
 
-    def aggregate(self, client_updates: Updates, num_examples: List[int]) -> List[torch.Tensor]:
-        # the size rules first: a list input is not even copied to the device
-        self._nremove(client_updates.K if isinstance(client_updates, ClientMatrix) else len(client_updates))
-        return super().aggregate(client_updates, num_examples)
+    def _check_clients(self, K: int) -> None:
+        self._nremove(K)
 
     def _publish(self) -> None:
         """The kept set and the last iteration's scores, fetched once per call."""

@@ -31,6 +31,9 @@ from .base_defense import BaseDefense, as_matrix, source_device
 
 
 class FLTrustDefense(BaseDefense):
+    # the server update starts from the round's global model (required: no center is resolved)
+    takes_global = True
+
     def __init__(self, defense_config: Dict[str, Any]):
         super().__init__(defense_config)
         self.root_dataset_size = defense_config.get("root_dataset_size", 100)

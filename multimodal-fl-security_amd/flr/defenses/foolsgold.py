@@ -27,21 +27,20 @@ are asked for.
 """
 from __future__ import annotations
 
-import math
-import numbers
-from typing import Any, Dict, List, Optional, Sequence, Union
+from typing import Any, Dict, List, Optional
 
 import torch
 
 from .. import ops
 from ..matrix import ClientMatrix, padded_ld
-from .base_defense import BaseDefense, Updates, as_matrix, source_device
+from ._config import real_in
+from .base_defense import CenteredDefense, Updates
 
 DEFAULT_CONFIDENCE = 1.0
 MAX_CLIENTS = ops.FOOLSGOLD_MAX_CLIENTS  # one lane per client in the weights workgroup
 
 
-class FoolsGoldDefense(BaseDefense):
+class FoolsGoldDefense(CenteredDefense):
     """Config: confidence — kappa, a finite float > 0 (default 1.0, the
     paper's); use_memory — bool (default True): the similarity is taken on the
     per-client running sum of updates, a K x P float32 matrix kept on the
@@ -49,11 +48,8 @@ class FoolsGoldDefense(BaseDefense):
     and one more pass over the client matrix per call; False: on this call's
     updates alone, no history is allocated.
 
-    The center of a call (the global model g the updates are taken from), in
-    this order: global_flat when given (the round engine's path); the vector of
-    set_center(), used by the next call only; this object's own previous result
-    when it has the same length; on a first call the coordinate-wise lower
-    median of the rows.
+    The global model g the updates are taken from is the call's center
+    (CenteredDefense).
 
     When every weight is 0 (all clients alike, or every row non-finite) the
     result is the center: no update (get_metrics()["no_update"]).  A client
@@ -70,17 +66,12 @@ class FoolsGoldDefense(BaseDefense):
 
     def __init__(self, defense_config: Dict[str, Any]):
         super().__init__(defense_config)
-        k = defense_config.get("confidence", DEFAULT_CONFIDENCE)
-        if isinstance(k, bool) or not isinstance(k, numbers.Real) or math.isnan(k) or math.isinf(k) or k <= 0:
-            raise ValueError(f"confidence must be a finite number > 0, got {k!r}")
-        self.confidence = float(k)
+        self.confidence = real_in(defense_config, "confidence", DEFAULT_CONFIDENCE, 0.0)
         m = defense_config.get("use_memory", True)
         if not isinstance(m, bool):
             raise ValueError(f"use_memory must be a bool, got {m!r}")
         self.use_memory = m
         self.calls = 0
-        self._center: Optional[torch.Tensor] = None    # set_center's vector, for the next call
-        self._previous: Optional[torch.Tensor] = None  # the last result (a tensor of this object's own)
         self._history: Optional[torch.Tensor] = None   # H, float32 [K, P]
         self._alpha = self._beta = self._maxcos = self._flags = None  # device results of the last call
 
@@ -92,16 +83,8 @@ class FoolsGoldDefense(BaseDefense):
         if K > MAX_CLIENTS:
             raise ValueError(f"FoolsGold handles at most {MAX_CLIENTS} clients, got {K}")
 
-    def set_center(self, center: Union[torch.Tensor, Sequence[torch.Tensor], None]) -> None:
-        """The global model of the next aggregate call (a flat vector or a
-        parameter list); None withdraws it.  The calls after that continue from
-        their own previous result."""
-        if center is None:
-            self._center = None
-        elif isinstance(center, torch.Tensor):
-            self._center = center.detach().reshape(-1).float()
-        else:
-            self._center = torch.cat([p.detach().reshape(-1).float() for p in center])
+    def _check_clients(self, K: int) -> None:
+        self._check_size(K)
 
     def reset(self) -> None:
         """Drops the history (its memory returns to the allocator): the next
@@ -112,24 +95,16 @@ class FoolsGoldDefense(BaseDefense):
         """H, float32 [K, P] on the device (None without memory or before a call)."""
         return self._history
 
-    def _start(self, cm: ClientMatrix, global_flat: Optional[torch.Tensor]) -> torch.Tensor:
-        given = global_flat if global_flat is not None else self._center
-        if given is not None:
-            if given.numel() != cm.P:
-                raise ValueError(f"the center holds {given.numel()} coordinates, the updates {cm.P}")
-            return given.detach().reshape(-1).to(device=cm.device, dtype=torch.float32).contiguous()
-        if self._previous is not None and self._previous.numel() == cm.P and self._previous.device == cm.device:
-            return self._previous
-        return ops.median_lower(cm.X)
-
     def aggregate_flat(self, cm: ClientMatrix, num_examples: List[int],
                        global_flat: Optional[torch.Tensor] = None) -> torch.Tensor:
+        # the size rules before the center is resolved: set_center's vector outlives a refused call
         self._check_size(cm.K)
         if self._history is not None and tuple(self._history.shape) != (cm.K, cm.P):
             raise ValueError(f"the history holds {self._history.shape[0]} clients x {self._history.shape[1]} "
                              f"coordinates, this call {cm.K} x {cm.P}: reset() starts a new one")
-        g = self._start(cm, global_flat)
-        self._center = None
+        return super().aggregate_flat(cm, num_examples, global_flat)
+
+    def _rule(self, cm: ClientMatrix, num_examples: List[int], g: torch.Tensor) -> torch.Tensor:
         if self.use_memory:
             if self._history is None or self._history.device != cm.device:
                 # the client matrix's padded row stride: the kernels' 16-byte loads
@@ -143,21 +118,7 @@ class FoolsGoldDefense(BaseDefense):
                                                                                    diagnostics=True)
         out = ops.rows_combine_from(cm.X, g, self._beta)
         self.calls += 1
-        self._previous = out
         return out
-
-    def aggregate(self, client_updates: Updates, num_examples: List[int],
-                  global_params: Optional[List[torch.Tensor]] = None) -> List[torch.Tensor]:
-        # the size rules first: a list input is not even copied to the device
-        self._check_size(client_updates.K if isinstance(client_updates, ClientMatrix) else len(client_updates))
-        cm = as_matrix(client_updates)
-        gflat = None
-        if global_params is not None:
-            gflat = torch.cat([p.detach().reshape(-1).float() for p in global_params])
-        flat = self.aggregate_flat(cm, num_examples, gflat)
-        # a copy: the caller may update the returned parameters in place, and
-        # the next call starts from this result
-        return cm.unflatten(flat.clone(), source_device(client_updates))
 
     @property
     def client_weights(self) -> List[float]:

@@ -15,7 +15,7 @@ import torch
 
 from .. import ops
 from ..matrix import ClientMatrix
-from .base_defense import BaseDefense, Updates, as_matrix, source_device
+from .base_defense import BaseDefense, Updates, as_matrix
 
 
 class DeadTaps(NamedTuple):
@@ -62,26 +62,54 @@ class KrumDefense(BaseDefense):
         self.scores_device = None
         self.order_device = None
 
-    def select(self, cm: ClientMatrix) -> torch.Tensor:
-        """Distances, scores and order on the device; returns the int32 order."""
-        n, f = cm.K, self.num_malicious
+    # One sequence for a ClientMatrix (aggregate_flat, select) and for a rank's
+    # CoordSlice (aggregate_sharded): the size rule, the distances, the
+    # refine-capacity check, _pick(), publish() if asked, _combine().  The
+    # subclasses override _sizes, _pick, _combine and publish.
+
+    def _sizes(self, n: int) -> None:
+        """The size rule for n clients; raises before any device work."""
+        f = self.num_malicious
         if n < 2 * f + 3:  # krum.py:153-157
             raise ValueError(
                 f"Krum requires n >= 2f + 3. Got n={n}, f={f}. Need at least {2 * f + 3} clients.")
-        ref = self.pairwise_method == "reference"
-        self.distances = ops.pairwise_l2(cm.X, self.pairwise_method, comm=self.comm,
-                                         tap_blocks=self.tap_blocks if ref else None,
-                                         dead=self.dead and self.dead.taps if ref and self.tap_blocks else None)
-        self._check_refine_capacity(n)
-        self.scores_device, self.order_device = ops.krum_select(self.distances, f)
+
+    def _pick(self) -> torch.Tensor:
+        """Scores and order from self.distances; returns the int32 order."""
+        self.scores_device, self.order_device = ops.krum_select(self.distances, self.num_malicious)
         return self.order_device
 
-    def _selected_row_filled(self, data: torch.Tensor, n: int) -> torch.Tensor:
-        """Single Krum's selected row data[i, :n], a copy with the unwritten
-        dead ranges filled in."""
-        i = int(self.order_device[0].item())
-        d = self.dead
-        return ops.fill_dead_ranges(data[i, :n].clone(), d.ranges, d.g, i < d.nneg)
+    def _run(self, src, publish: bool, events=None) -> torch.Tensor:
+        self._sizes(src.K)
+        if isinstance(src, ClientMatrix):
+            ref = self.pairwise_method == "reference"
+            self.distances = ops.pairwise_l2(src.X, self.pairwise_method, comm=self.comm,
+                                             tap_blocks=self.tap_blocks if ref else None,
+                                             dead=self.dead and self.dead.taps if ref and self.tap_blocks else None)
+        else:
+            self.distances = self._sharded_distances(src, events)
+        self._check_refine_capacity(src.K)
+        order = self._pick()
+        if publish:
+            self.publish()
+        return order
+
+    def select(self, cm: ClientMatrix) -> torch.Tensor:
+        """Distances, scores and order on the device; returns the int32 order."""
+        return self._run(cm, publish=False)
+
+    def _combine(self, src, order: torch.Tensor) -> torch.Tensor:
+        """The Multi-Krum mean of src's columns, or single Krum's selected row."""
+        if self.multi_k != 1:
+            return ops.rows_mean(src.X, order[: min(self.multi_k, src.K)], divisor=self.multi_k,
+                                 dead=self.dead and self.dead.rows)
+        n = src.X.shape[1]
+        if self.dead is not None:  # one GPU: a slice is the whole matrix
+            i = int(order[0].item())
+            d = self.dead  # a copy of the row with the unwritten dead ranges filled in
+            return ops.fill_dead_ranges(src.data[i, :n].clone(), d.ranges, d.g, i < d.nneg)
+        # a view of the whole row (one 4-byte read); a rank's slice stays on the stream
+        return src.data[int(order[0].item()) if isinstance(src, ClientMatrix) else order[0].long(), :n]
 
     def _check_refine_capacity(self, K: int) -> None:
         """The Gram path's refine list holds 128 rows: every row at K <= 128.
@@ -97,15 +125,7 @@ class KrumDefense(BaseDefense):
     def aggregate_flat(self, cm: ClientMatrix, num_examples: List[int], publish: bool = True) -> torch.Tensor:
         """Device pipeline; with publish=False the host copies of the scores
         and indices are skipped (no device sync) — call publish() later."""
-        order = self.select(cm)
-        if publish:
-            self.publish()
-        if self.multi_k == 1:
-            if self.dead is not None:
-                return self._selected_row_filled(cm.data, cm.P)
-            return cm.data[int(order[0].item()), : cm.P]
-        return ops.rows_mean(cm.X, order[: min(self.multi_k, cm.K)], divisor=self.multi_k,
-                             dead=self.dead and self.dead.rows)
+        return self._combine(cm, self._run(cm, publish))
 
     # pairwise_method="reference" reproduces the reference's torch.norm
     # accumulation, which runs over the whole vector in parameters() order:
@@ -132,26 +152,8 @@ class KrumDefense(BaseDefense):
     def aggregate_sharded(self, cs, num_examples: List[int], publish: bool = True, events=None) -> torch.Tensor:
         """Coordinate-sharded Krum (flr.shard): distances from the per-slice
         Gram sums of every GPU (bit-identical to the one-GPU D), scores and
-        order replicated, then the Multi-Krum mean of this GPU's range."""
-        self._select_sharded(cs, publish, events)
-        if self.multi_k == 1:
-            if self.dead is not None:  # one GPU: the slice is the whole matrix
-                return self._selected_row_filled(cs.data, cs.n)
-            return cs.data[self.order_device[0].long(), : cs.n]
-        return ops.rows_mean(cs.X, self.order_device[: min(self.multi_k, cs.K)], divisor=self.multi_k,
-                             dead=self.dead and self.dead.rows)
-
-    def _select_sharded(self, cs, publish: bool, events=None) -> None:
-        """select() of a coordinate slice, then publish() if asked."""
-        n, f = cs.K, self.num_malicious
-        if n < 2 * f + 3:  # krum.py:153-157
-            raise ValueError(
-                f"Krum requires n >= 2f + 3. Got n={n}, f={f}. Need at least {2 * f + 3} clients.")
-        self.distances = self._sharded_distances(cs, events)
-        self._check_refine_capacity(n)
-        self.scores_device, self.order_device = ops.krum_select(self.distances, f)
-        if publish:
-            self.publish()
+        order replicated, then the combination of this GPU's range."""
+        return self._combine(cs, self._run(cs, publish, events))
 
     def _sharded_distances(self, cs, events=None):
         if self.pairwise_method == "reference":
@@ -176,14 +178,12 @@ class KrumDefense(BaseDefense):
         self.rejected_clients = order_host[self.multi_k:]
 
     def aggregate(self, client_updates: Updates, num_examples: List[int]) -> List[torch.Tensor]:
-        cm = as_matrix(client_updates)
-        if self.multi_k == 1:  # single Krum returns the caller's own list (krum.py:178-181)
-            self.select(cm)
-            self.publish()
-            sel = self.selected_clients[0]
-            return cm.row(sel) if isinstance(client_updates, ClientMatrix) else client_updates[sel]
-        flat = self.aggregate_flat(cm, num_examples)
-        return cm.unflatten(flat, source_device(client_updates))
+        if self.multi_k != 1:
+            return super().aggregate(client_updates, num_examples)
+        cm = as_matrix(client_updates)  # single Krum returns the caller's own list (krum.py:178-181)
+        self._run(cm, publish=True)
+        sel = self.selected_clients[0]
+        return cm.row(sel) if isinstance(client_updates, ClientMatrix) else client_updates[sel]
 
     def detect_malicious(self, client_updates: Updates, num_examples: List[int]) -> List[int]:
         if not self.client_scores:
@@ -234,28 +234,16 @@ class KrumTrimmedMeanDefense(KrumDefense):
     # the trimmed mean reads the selected rows whole: no dead-tap deferral
     supports_dead_rows = False
 
-    def _combine(self, X: torch.Tensor, order: torch.Tensor) -> torch.Tensor:
-        m = min(self.multi_k, X.shape[0])
+    def _combine(self, src, order: torch.Tensor) -> torch.Tensor:
+        m = min(self.multi_k, src.K)
         t = max(1, int(m * self.trim_ratio))
         self.num_trimmed_per_end = t
         sel = order[:m]
         if m - 2 * t < 1:
-            return ops.median_lower(X, rows=sel)
-        return ops.trimmed_mean(X, t, rows=sel)
+            return ops.median_lower(src.X, rows=sel)
+        return ops.trimmed_mean(src.X, t, rows=sel)
 
-    def aggregate_flat(self, cm: ClientMatrix, num_examples: List[int], publish: bool = True) -> torch.Tensor:
-        order = self.select(cm)
-        if publish:
-            self.publish()
-        return self._combine(cm.X, order)
-
-    def aggregate_sharded(self, cs, num_examples: List[int], publish: bool = True, events=None) -> torch.Tensor:
-        self._select_sharded(cs, publish, events)
-        return self._combine(cs.X, self.order_device)
-
-    def aggregate(self, client_updates: Updates, num_examples: List[int]) -> List[torch.Tensor]:
-        cm = as_matrix(client_updates)
-        return cm.unflatten(self.aggregate_flat(cm, num_examples), source_device(client_updates))
+    aggregate = BaseDefense.aggregate  # a combination at multi_k == 1 too: not single Krum's own list entry
 
     def get_metrics(self) -> Dict[str, Any]:
         m = super().get_metrics()

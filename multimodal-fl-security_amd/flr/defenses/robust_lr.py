@@ -32,13 +32,14 @@ from __future__ import annotations
 
 import math
 import numbers
-from typing import Any, Dict, List, Optional, Sequence, Union
+from typing import Any, Dict, List, Optional, Union
 
 import torch
 
 from .. import ops
 from ..matrix import ClientMatrix
-from .base_defense import BaseDefense, Updates, as_matrix, source_device
+from ._config import real_in
+from .base_defense import CenteredDefense, Updates
 from .trimmed_mean import MedianDefense, TrimmedMeanDefense
 
 DEFAULT_THRESHOLD = 0.25
@@ -46,7 +47,7 @@ DEFAULT_SERVER_LR = 1.0
 _BASES = {"fedavg": None, "median": MedianDefense, "trimmed_mean": TrimmedMeanDefense}
 
 
-class RobustLRDefense(BaseDefense):
+class RobustLRDefense(CenteredDefense):
     """Config: threshold — an int in [0, K] (checked against K at the call), or
     a float in (0, 1) meaning ceil(threshold * K); the default, 0.25, is this
     project's choice (the paper's guidance is only that the threshold must exceed
@@ -55,11 +56,8 @@ class RobustLRDefense(BaseDefense):
     "trimmed_mean", configured by base_cfg.  server_lr — a finite float > 0,
     default 1.0.
 
-    The center of a call (the global model the clients started from), in this
-    order: global_flat when given (the round engine's path); the vector of
-    set_center(), used by the next call only; this object's own previous result
-    when it has the same length; on a first call the coordinate-wise lower median
-    of the rows.
+    The global model g the clients started from is the call's center
+    (CenteredDefense).
 
     num_examples weighs the FedAvg base only; the vote is one client, one vote."""
 
@@ -86,13 +84,7 @@ class RobustLRDefense(BaseDefense):
             raise ValueError(f"base must be one of {', '.join(_BASES)}, got {base!r}")
         self.base = base
         self._base = None if _BASES[base] is None else _BASES[base](dict(defense_config.get("base_cfg") or {}))
-        lr = defense_config.get("server_lr", DEFAULT_SERVER_LR)
-        if isinstance(lr, bool) or not isinstance(lr, numbers.Real) or not math.isfinite(lr) or lr <= 0 \
-                or not 0.0 < float(torch.tensor(float(lr), dtype=torch.float32)) < float("inf"):
-            raise ValueError(f"server_lr must be a finite number > 0 (in float32), got {lr!r}")
-        self.server_lr = float(lr)
-        self._center: Optional[torch.Tensor] = None    # set_center's vector, for the next call
-        self._previous: Optional[torch.Tensor] = None  # the last result (a tensor of this object's own)
+        self.server_lr = real_in(defense_config, "server_lr", DEFAULT_SERVER_LR, 0.0, float32=True)
         self._votes: Optional[torch.Tensor] = None     # device diagnostics of the last call
         self._flipped: Optional[torch.Tensor] = None
         self._theta: Optional[int] = None              # the threshold the last call resolved
@@ -105,68 +97,25 @@ class RobustLRDefense(BaseDefense):
             return self.threshold
         return min(K, math.ceil(self.threshold * K))
 
-    def set_center(self, center: Union[torch.Tensor, Sequence[torch.Tensor], None]) -> None:
-        """The global model of the next aggregate call (a flat vector or a
-        parameter list, e.g. the initial global model); None withdraws it.  The
-        calls after that are centred on their own previous result."""
-        if center is None:
-            self._center = None
-        elif isinstance(center, torch.Tensor):
-            self._center = center.detach().reshape(-1).float()
-        else:
-            self._center = torch.cat([p.detach().reshape(-1).float() for p in center])
-
-    def _start(self, X: torch.Tensor, given: Optional[torch.Tensor]) -> torch.Tensor:
-        P = X.shape[1]
-        if given is not None:
-            if given.numel() != P:
-                raise ValueError(f"the center holds {given.numel()} coordinates, the updates {P}")
-            return given.detach().reshape(-1).to(device=X.device, dtype=torch.float32).contiguous()
-        if self._previous is not None and self._previous.numel() == P and self._previous.device == X.device:
-            return self._previous
-        return ops.median_lower(X)
-
-    def _rule(self, X: torch.Tensor, num_examples: List[int], g: torch.Tensor, base_aggregate) -> torch.Tensor:
+    def _rule(self, src, num_examples: List[int], g: torch.Tensor) -> torch.Tensor:
+        """src: the client matrix, or one rank's coordinate slice of it."""
+        X = src.X
         theta = self.resolve_threshold(X.shape[0])
         if self._base is None:
             out, votes, flipped = ops.rlr_fedavg(X, list(num_examples), g, theta, self.server_lr, diagnostics=True)
         else:
-            agg = base_aggregate()
+            base = self._base.aggregate_flat if isinstance(src, ClientMatrix) else self._base.aggregate_sharded
+            agg = base(src, num_examples)
             votes = ops.sign_vote(X, g)
             out, flipped = ops.rlr_apply(agg, g, votes, theta, self.server_lr, out=agg, count=True)
         self._theta, self._votes, self._flipped = theta, votes, flipped
-        self._previous = out
         return out
-
-    def aggregate_flat(self, cm: ClientMatrix, num_examples: List[int],
-                       global_flat: Optional[torch.Tensor] = None) -> torch.Tensor:
-        g = self._start(cm.X, global_flat if global_flat is not None else self._center)
-        self._center = None
-        return self._rule(cm.X, num_examples, g, lambda: self._base.aggregate_flat(cm, num_examples))
 
     def aggregate_sharded(self, cs, num_examples: List[int],
                           global_flat: Optional[torch.Tensor] = None) -> torch.Tensor:
         """One rank's coordinate range [cs.begin, cs.end): global_flat is the
         center's slice of that range; set_center's vector is the whole model."""
-        given = global_flat
-        if given is None and self._center is not None:
-            if self._center.numel() != cs.P:
-                raise ValueError(f"the center holds {self._center.numel()} coordinates, the updates {cs.P}")
-            given = self._center[cs.begin:cs.end]
-        g = self._start(cs.X, given)
-        self._center = None
-        return self._rule(cs.X, num_examples, g, lambda: self._base.aggregate_sharded(cs, num_examples))
-
-    def aggregate(self, client_updates: Updates, num_examples: List[int],
-                  global_params: Optional[List[torch.Tensor]] = None) -> List[torch.Tensor]:
-        cm = as_matrix(client_updates)
-        gflat = None
-        if global_params is not None:
-            gflat = torch.cat([p.detach().reshape(-1).float() for p in global_params])
-        flat = self.aggregate_flat(cm, num_examples, gflat)
-        # a copy: the caller may update the returned parameters in place, and
-        # the next call is centred on this result
-        return cm.unflatten(flat.clone(), source_device(client_updates))
+        return self._aggregate(cs, num_examples, global_flat, cs.begin, cs.P)
 
     def votes(self) -> Optional[torch.Tensor]:
         """The last call's votes: a device int32 [P] tensor (None before a call)."""

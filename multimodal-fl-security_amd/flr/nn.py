@@ -6,10 +6,7 @@ import os
 import torch
 
 from . import _capi
-
-
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
+from ._capi import ptr as _ptr, stream_of as _stream
 
 
 def _workspace(geom, device):
@@ -291,10 +288,6 @@ class ClientGRU(torch.autograd.Function):
 
 def client_gru(gi: torch.Tensor, whh: torch.Tensor, bhh: torch.Tensor) -> torch.Tensor:
     return ClientGRU.apply(gi, whh, bhh)
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 class ClientBatchNorm(torch.autograd.Function):

@@ -14,18 +14,11 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import _capi
+from ._capi import ptr as _ptr, stream_of as _stream
 
 CHUNK = 64  # coordinates per pairwise chunk; client matrices pad ldx to this
 PW_SLICES = 8  # FLR_PW_SLICES: canonical coordinate slices of the pairwise kernels
 REFINE_ROWS = 128  # far-cluster rows the Gram path refines per call (include/flr.h, a9)
-
-
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
-    return None if t is None else t.data_ptr()
 
 
 def _check_matrix(X: torch.Tensor, name: str = "X") -> Tuple[int, int, int]:
@@ -35,6 +28,37 @@ def _check_matrix(X: torch.Tensor, name: str = "X") -> Tuple[int, int, int]:
         raise ValueError(f"{name} must be a row-major float32 [K, P] matrix (got {X.dtype}, "
                          f"shape {tuple(X.shape)}, strides {X.stride()})")
     return X.shape[0], X.shape[1], X.stride(0)
+
+
+def _check_vector(t, n: int, device, name: str, dtype=torch.float32) -> None:
+    if not isinstance(t, torch.Tensor) or t.device != device or t.dtype != dtype or not t.is_contiguous() \
+            or t.numel() != n:
+        raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} [{n}] vector on {device}")
+
+
+def _out_vector(out: Optional[torch.Tensor], n: int, device, dtype=torch.float32,
+                name: Optional[str] = "out") -> torch.Tensor:
+    """A new output vector, or the caller's, checked (name=None: taken as it
+    is, by the ops that never checked theirs)."""
+    if out is None:
+        return torch.empty(n, dtype=dtype, device=device)
+    if name is not None:
+        _check_vector(out, n, device, name, dtype)
+    return out
+
+
+def _examples(num_examples, K: int, device) -> torch.Tensor:
+    """num_examples as the int64 [K] device vector of the FedAvg kernels."""
+    n = torch.as_tensor(num_examples, dtype=torch.int64).to(device).contiguous()
+    if n.numel() != K:
+        raise ValueError(f"num_examples has {n.numel()} entries for {K} clients")
+    return n
+
+
+def _ws(nbytes: int, device) -> Tuple[torch.Tensor, int]:
+    """A workspace of nbytes and its 256-byte aligned address inside it."""
+    ws = torch.empty(max(nbytes, 256) + 256, dtype=torch.uint8, device=device)
+    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256
 
 
 def pairwise_l2(X: torch.Tensor, method: str = "gram", events=None, comm=None,
@@ -91,13 +115,12 @@ def pairwise_l2(X: torch.Tensor, method: str = "gram", events=None, comm=None,
     else:
         raise ValueError(f"unknown pairwise method {method!r}")
     nbytes = int(getattr(_capi.lib(), ws_fn)(K, P))
-    ws = torch.empty(max(nbytes, 256) + 256, dtype=torch.uint8, device=X.device)
-    off = (-ws.data_ptr()) % 256
+    ws, wp = _ws(nbytes, X.device)
     if events is not None and method == "gram":
-        _capi.call("flr_pairwise_l2_ex", X.data_ptr(), K, P, ldx, D.data_ptr(), ws.data_ptr() + off, nbytes,
-                   _stream(X), events[0], events[1])
+        _capi.call("flr_pairwise_l2_ex", X.data_ptr(), K, P, ldx, D.data_ptr(), wp, nbytes, _stream(X), events[0],
+                   events[1])
     else:
-        _capi.call(fn, X.data_ptr(), K, P, ldx, D.data_ptr(), ws.data_ptr() + off, nbytes, _stream(X))
+        _capi.call(fn, X.data_ptr(), K, P, ldx, D.data_ptr(), wp, nbytes, _stream(X))
     return D
 
 
@@ -125,9 +148,9 @@ def krum_select_iter(D: torch.Tensor, f: int, theta: int) -> Tuple[torch.Tensor,
     scores = torch.empty(K, dtype=torch.float64, device=D.device)
     picked = torch.empty(K, dtype=torch.int32, device=D.device)
     nbytes = int(_capi.lib().flr_krum_select_iter_workspace(K))
-    ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=D.device)
+    ws, wp = _ws(nbytes, D.device)
     _capi.call("flr_krum_select_iter", D.data_ptr(), K, int(f), int(theta), scores.data_ptr(), picked.data_ptr(),
-               ws.data_ptr(), nbytes, _stream(D))
+               wp, nbytes, _stream(D))
     return scores, picked
 
 
@@ -141,8 +164,7 @@ def rows_mean(X: torch.Tensor, rows: torch.Tensor, divisor: Optional[int] = None
     rows = rows.to(device=X.device, dtype=torch.int32).contiguous()
     m = rows.numel()
     divisor = m if divisor is None else int(divisor)
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=X.device)
+    out = _out_vector(out, P, X.device, name=None)
     if dead is None:
         _capi.call("flr_rows_mean", X.data_ptr(), K, P, ldx, rows.data_ptr(), m, divisor, out.data_ptr(),
                    _stream(X))
@@ -168,11 +190,8 @@ def fill_dead_ranges(vec: torch.Tensor, ranges, gdead: torch.Tensor, negate: boo
 def fedavg(X: torch.Tensor, num_examples, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Example-weighted average (base_defense.py:80-97)."""
     K, P, ldx = _check_matrix(X)
-    n = torch.as_tensor(num_examples, dtype=torch.int64).to(X.device).contiguous()
-    if n.numel() != K:
-        raise ValueError(f"num_examples has {n.numel()} entries for {K} clients")
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=X.device)
+    n = _examples(num_examples, K, X.device)
+    out = _out_vector(out, P, X.device, name=None)
     _capi.call("flr_fedavg", X.data_ptr(), K, P, ldx, n.data_ptr(), out.data_ptr(), _stream(X))
     return out
 
@@ -186,8 +205,7 @@ def trimmed_mean(X: torch.Tensor, t: int, out: Optional[torch.Tensor] = None,
     """Coordinate-wise mean of sorted ranks [t, m-t) (trimmed_mean.py:74-88)
     over all K rows, or over the row subset `rows` (m = len(rows))."""
     K, P, ldx = _check_matrix(X)
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=X.device)
+    out = _out_vector(out, P, X.device, name=None)
     if rows is None:
         _capi.call("flr_trimmed_mean", X.data_ptr(), K, P, ldx, int(t), out.data_ptr(), _stream(X))
     else:
@@ -201,8 +219,7 @@ def median_lower(X: torch.Tensor, out: Optional[torch.Tensor] = None,
                  rows: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Coordinate-wise lower median (trimmed_mean.py:101, 163), optionally of a row subset."""
     K, P, ldx = _check_matrix(X)
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=X.device)
+    out = _out_vector(out, P, X.device, name=None)
     if rows is None:
         _capi.call("flr_median_lower", X.data_ptr(), K, P, ldx, out.data_ptr(), _stream(X))
     else:
@@ -218,8 +235,7 @@ def median_window_mean(X: torch.Tensor, beta: int, rows: Optional[torch.Tensor] 
     of the beta values closest to the lower median, over all K rows or over
     the row subset `rows` (at most 128 rows either way)."""
     K, P, ldx = _check_matrix(X)
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=X.device)
+    out = _out_vector(out, P, X.device, name=None)
     r = None if rows is None else _rows_arg(rows, X.device)
     m = K if r is None else r.numel()
     _capi.call("flr_median_window_mean_rows", X.data_ptr(), K, P, ldx, _ptr(r), m, int(beta), out.data_ptr(),
@@ -239,9 +255,8 @@ def collude_rows(X: torch.Tensor, nmal: int, mode: int, param: float, mean_out: 
     receive them."""
     K, P, ldx = _check_matrix(X)
     for name, t in (("mean_out", mean_out), ("std_out", std_out)):
-        if t is not None and (t.device != X.device or t.dtype != torch.float32 or not t.is_contiguous()
-                              or t.numel() != P):
-            raise ValueError(f"{name} must be a contiguous float32 [{P}] vector on {X.device}")
+        if t is not None:
+            _check_vector(t, P, X.device, name)
     _capi.call("flr_collude_rows", X.data_ptr(), K, P, ldx, int(nmal), int(mode), float(param), _ptr(mean_out),
                _ptr(std_out), _stream(X))
 
@@ -263,10 +278,8 @@ def minmax_rows(X: torch.Tensor, nmal: int, objective: int, perturb: int, global
     with diagnostics (gamma, stats float64 [2 * nb + 4] — a_i, b_i, c, R2, S,
     the bound used —, mu float32 [P], sigma float32 [P]) as device tensors."""
     K, P, ldx = _check_matrix(X)
-    if global_flat is not None and (not isinstance(global_flat, torch.Tensor) or global_flat.device != X.device
-                                    or global_flat.dtype != torch.float32 or not global_flat.is_contiguous()
-                                    or global_flat.numel() != P):
-        raise ValueError(f"global_flat must be a contiguous float32 [{P}] vector on {X.device}")
+    if global_flat is not None:
+        _check_vector(global_flat, P, X.device, "global_flat")
     nmal = int(nmal)
     gamma = torch.empty((), dtype=torch.float64, device=X.device)
     stats = None
@@ -294,19 +307,13 @@ def centered_clip(X: torch.Tensor, v0: torch.Tensor, tau: float, iters: int, out
     float64 [iters, K], scales float32 [iters, K], taus float32 [iters]) as
     device tensors."""
     K, P, ldx = _check_matrix(X)
-    for name, t in (("v0", v0), ("out", out)):
-        if t is not None and (not isinstance(t, torch.Tensor) or t.device != X.device or t.dtype != torch.float32
-                              or not t.is_contiguous() or t.numel() != P):
-            raise ValueError(f"{name} must be a contiguous float32 [{P}] vector on {X.device}")
-    if v0 is None:
-        raise ValueError("v0 must be a float32 device vector of length P")
+    _check_vector(v0, P, X.device, "v0")
+    out = _out_vector(out, P, X.device)
     tau, iters = float(tau), int(iters)
     if not tau >= 0.0:
         raise ValueError(f"tau must be >= 0 (0: the median of the distances), got {tau}")
     if iters < 1:
         raise ValueError(f"iters must be >= 1, got {iters}")
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=X.device)
     norms = scales = taus = None
     if diagnostics:
         norms = torch.empty((iters, K), dtype=torch.float64, device=X.device)
@@ -366,24 +373,13 @@ def rows_mean_keep(X: torch.Tensor, keep: torch.Tensor, out: Optional[torch.Tens
     on X's device, counted there): the bits of rows_mean over the ascending kept
     rows; NaN everywhere when no row is kept.  Only the kept rows are read."""
     K, P, ldx = _check_matrix(X)
-    if not isinstance(keep, torch.Tensor) or keep.device != X.device or keep.dtype != torch.int32 \
-            or not keep.is_contiguous() or keep.numel() != K:
-        raise ValueError(f"keep must be a contiguous int32 [{K}] vector on {X.device}")
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=X.device)
-    elif out.device != X.device or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != P:
-        raise ValueError(f"out must be a contiguous float32 [{P}] vector on {X.device}")
+    _check_vector(keep, K, X.device, "keep", torch.int32)
+    out = _out_vector(out, P, X.device)
     _capi.call("flr_rows_mean_keep", X.data_ptr(), K, P, ldx, keep.data_ptr(), out.data_ptr(), _stream(X))
     return out
 
 
 FOOLSGOLD_MAX_CLIENTS = 1024  # flr_rows_gram's and flr_foolsgold_weights' limit
-
-
-def _check_vector(t, n: int, device, name: str, dtype=torch.float32) -> None:
-    if not isinstance(t, torch.Tensor) or t.device != device or t.dtype != dtype or not t.is_contiguous() \
-            or t.numel() != n:
-        raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} [{n}] vector on {device}")
 
 
 def rows_accumulate_(H: torch.Tensor, X: torch.Tensor, center: torch.Tensor) -> torch.Tensor:
@@ -472,12 +468,9 @@ def rows_combine_from(X: torch.Tensor, center: torch.Tensor, beta: torch.Tensor,
         raise ValueError(f"rows_combine_from handles at most 4096 rows, got {K}")
     _check_vector(center, P, X.device, "center")
     _check_vector(beta, K, X.device, "beta")
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=X.device)
-    else:
-        _check_vector(out, P, X.device, "out")
-        if out.data_ptr() == center.data_ptr():
-            raise ValueError("out must not be center")
+    out = _out_vector(out, P, X.device)
+    if out.data_ptr() == center.data_ptr():
+        raise ValueError("out must not be center")
     _capi.call("flr_rows_combine_from", X.data_ptr(), K, P, ldx, center.data_ptr(), beta.data_ptr(), out.data_ptr(),
                _stream(X))
     return out
@@ -498,10 +491,7 @@ def sign_vote(X: torch.Tensor, g: torch.Tensor, out: Optional[torch.Tensor] = No
     votes 0 and -0 against +0 votes 0.  g: float32 [P] on X's device."""
     K, P, ldx = _check_matrix(X)
     _check_vector(g, P, X.device, "g")
-    if out is None:
-        out = torch.empty(P, dtype=torch.int32, device=X.device)
-    else:
-        _check_vector(out, P, X.device, "out", torch.int32)
+    out = _out_vector(out, P, X.device, torch.int32)
     _capi.call("flr_sign_vote", X.data_ptr(), K, P, ldx, g.data_ptr(), out.data_ptr(), _stream(X))
     return out
 
@@ -520,10 +510,7 @@ def rlr_apply(agg: torch.Tensor, g: torch.Tensor, votes: torch.Tensor, theta: in
     _check_vector(g, P, agg.device, "g")
     _check_vector(votes, P, agg.device, "votes", torch.int32)
     theta, eta = _check_rlr(theta, eta, None)
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=agg.device)
-    else:
-        _check_vector(out, P, agg.device, "out")
+    out = _out_vector(out, P, agg.device)
     flipped = torch.empty(1, dtype=torch.int64, device=agg.device) if count else None
     _capi.call("flr_rlr_apply", agg.data_ptr(), g.data_ptr(), votes.data_ptr(), P, theta, eta, out.data_ptr(),
                _ptr(flipped), _stream(agg))
@@ -537,15 +524,10 @@ def rlr_fedavg(X: torch.Tensor, num_examples, g: torch.Tensor, theta: int, eta: 
     must not be g), or with diagnostics (out, votes int32 [P], flipped int64 [1])
     as device tensors."""
     K, P, ldx = _check_matrix(X)
-    n = torch.as_tensor(num_examples, dtype=torch.int64).to(X.device).contiguous()
-    if n.numel() != K:
-        raise ValueError(f"num_examples has {n.numel()} entries for {K} clients")
+    n = _examples(num_examples, K, X.device)
     _check_vector(g, P, X.device, "g")
     theta, eta = _check_rlr(theta, eta, K)
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=X.device)
-    else:
-        _check_vector(out, P, X.device, "out")
+    out = _out_vector(out, P, X.device)
     votes = flipped = None
     if diagnostics:
         votes = torch.empty(P, dtype=torch.int32, device=X.device)
@@ -563,28 +545,25 @@ def row_norms(X: torch.Tensor, center: Optional[torch.Tensor] = None, kind: str 
     if kind not in ("l2", "linf"):
         raise ValueError(f"unknown norm kind {kind!r}")
     if center is not None:
-        if not center.is_cuda or center.dtype != torch.float32 or center.numel() != P:
-            raise ValueError("center must be a float32 device vector of length P")
-        center = center.contiguous()
+        center = center.contiguous()  # a strided view is accepted
+        _check_vector(center, P, X.device, "center")
     out = torch.empty(K, dtype=torch.float64, device=X.device)
     nbytes = int(_capi.lib().flr_row_norms_workspace(K))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
+    ws, wp = _ws(nbytes, X.device)
     _capi.call("flr_row_norms", X.data_ptr(), K, P, ldx, _ptr(center), 0 if kind == "l2" else 1, out.data_ptr(),
-               ws.data_ptr(), nbytes, _stream(X))
+               wp, nbytes, _stream(X))
     return out
 
 
 def row_dots(X: torch.Tensor, v: torch.Tensor) -> torch.Tensor:
     """float64 [K]: X_i . v (fltrust.py:176), exact products, fp64 fixed-order sum."""
     K, P, ldx = _check_matrix(X)
-    if not v.is_cuda or v.dtype != torch.float32 or v.numel() != P:
-        raise ValueError("v must be a float32 device vector of length P")
-    v = v.contiguous()
+    v = v.contiguous()  # a strided view is accepted
+    _check_vector(v, P, X.device, "v")
     out = torch.empty(K, dtype=torch.float64, device=X.device)
     nbytes = int(_capi.lib().flr_row_norms_workspace(K))
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=X.device)
-    _capi.call("flr_row_dots", X.data_ptr(), K, P, ldx, v.data_ptr(), out.data_ptr(), ws.data_ptr(), nbytes,
-               _stream(X))
+    ws, wp = _ws(nbytes, X.device)
+    _capi.call("flr_row_dots", X.data_ptr(), K, P, ldx, v.data_ptr(), out.data_ptr(), wp, nbytes, _stream(X))
     return out
 
 
@@ -608,8 +587,7 @@ def weighted_rows(X: torch.Tensor, weights, divisor: float, rows=None, scales=No
         s = torch.as_tensor(scales, dtype=torch.float32).to(X.device).contiguous()
         if s.numel() != m:
             raise ValueError("scales and weights differ in length")
-    if out is None:
-        out = torch.empty(P, dtype=torch.float32, device=X.device)
+    out = _out_vector(out, P, X.device, name=None)
     _capi.call("flr_weighted_rows", X.data_ptr(), K, P, ldx, _ptr(r), m, w.data_ptr(), _ptr(s), float(divisor),
                out.data_ptr(), _stream(X))
     return out
@@ -642,11 +620,6 @@ def _ref_workspace(K: int, P: int, device, stream: int) -> Tuple[int, int]:
 def release_workspaces() -> None:
     """Drop the cached reference-exact workspaces (their HBM returns to torch's allocator)."""
     _REF_WS.clear()
-
-
-def _ws(nbytes: int, device) -> Tuple[torch.Tensor, int]:
-    ws = torch.empty(max(nbytes, 256) + 256, dtype=torch.uint8, device=device)
-    return ws, ws.data_ptr() + (-ws.data_ptr()) % 256
 
 
 def pairwise_l2_reference_sharded(cs, tap_blocks=None) -> torch.Tensor:

@@ -18,7 +18,6 @@ Both give the bit-identical global model at every GPU count.
 """
 from __future__ import annotations
 
-import inspect
 import logging
 import os
 from dataclasses import dataclass, field
@@ -161,9 +160,8 @@ class RoundEngine:
         self.use_graph = (rcfg.graph and self.device.type == "cuda" and os.environ.get("FLR_GRAPH", "1") != "0")
         self._graph = None
         self._graph_losses: Optional[torch.Tensor] = None
-        self._wants_global = "global_flat" in inspect.signature(self.defense.aggregate_flat).parameters
-        # the same for a rank's coordinate range: the defense takes the global model's slice
-        self._shard_wants_global = "global_flat" in inspect.signature(self.defense.aggregate_sharded).parameters
+        # the defense takes the round's global model (its slice, for a rank's coordinate range)
+        self._wants_global = self.defense.takes_global
         # training-order rounds (BaseDefense.order_free): the client matrix is in
         # the trainer's coordinate order, written by the last optimizer step;
         # gtrain is the global model in that order (FLR_ORDER=torch: off)
@@ -377,7 +375,7 @@ class RoundEngine:
         if self.exchange == "alltoall":
             cs = self._slice = self.xchg.exchange(self.trainer.X.data)
             self._apply_collusion(cs.X)  # coordinate-wise: this rank's slice needs no other
-            if self._shard_wants_global:  # the robust learning rate: global_flat is overwritten below
+            if self._wants_global:  # the robust learning rate: global_flat is overwritten below
                 kw["global_flat"] = self.global_flat[cs.begin:cs.end].clone()
             try:
                 part = self.defense.aggregate_sharded(cs, self.num_examples, **kw)

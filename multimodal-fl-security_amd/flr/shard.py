@@ -30,6 +30,7 @@ import torch
 import torch.distributed as dist
 
 from . import _capi
+from ._capi import stream_of as _stream
 from .ops import CHUNK
 
 PW_SLICES = 8  # FLR_PW_SLICES
@@ -231,10 +232,6 @@ def _copy(src: torch.Tensor, dst: torch.Tensor, n: int) -> None:
         _capi.call("flr_copy_rows", src.data_ptr(), w, w, dst.data_ptr(), w, 1, _stream(src))
     else:
         dst.reshape(-1)[:n].copy_(src.reshape(-1)[:n])
-
-
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream if t.is_cuda else 0
 
 
 def pack_for_exchange(local: torch.Tensor, P: int, plan: CoordPlan, send: torch.Tensor) -> None:

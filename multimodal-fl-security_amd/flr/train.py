@@ -28,14 +28,11 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import _capi
+from ._capi import stream_of as _stream
 from .matrix import ClientMatrix
 from .models import multimodal as _mm
 from .models.multimodal import (ModelSpec, batched_forward, conv_geometry, from_tap_major, live_taps, param_layout,
                                 tap_major_names, to_tap_major)
-
-
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 class CrossEntropy(torch.autograd.Function):

@@ -103,6 +103,35 @@ def test_sharded_defense_world1_equals_flat(cuda, name, cfg):
         assert d1.selected_clients == d2.selected_clients
 
 
+@pytest.mark.parametrize("method", ["reference", "gram"])
+@pytest.mark.parametrize("name,extra,nsel", [("krum", {"multi_k": 1}, 1), ("krum", {"multi_k": 5}, 5),
+                                             ("krum_trimmed_mean", {"multi_k": 5}, 5), ("bulyan", {}, 7)])
+def test_krum_family_sharded_equals_flat(cuda, name, extra, nsel, method):
+    """The Krum family's one pipeline over a ClientMatrix and over a world-1
+    CoordSlice: the same vector and the same selection, published by the call
+    or afterwards.  K = 11 is n = 4f + 3 at f = 2 (Bulyan's smallest), P = 257
+    leaves a ragged tail."""
+    K, P, f = 11, 257, 2
+    X = update_matrix(K, P, f=f, seed=23, device=cuda)
+    cm = ClientMatrix(X, P, [torch.Size([P])])
+    cs = CoordSlice(X, CoordPlan(P, 1), 0, Comm())
+    cfg = {"num_malicious": f, "pairwise_method": method, **extra}
+    ne = [1] * K
+    for publish in (True, False):
+        flat, shard = get_defense(name, dict(cfg)), get_defense(name, dict(cfg))
+        a = flat.aggregate_flat(cm, ne, publish=publish)
+        b = shard.aggregate_sharded(cs, ne, publish=publish)
+        if not publish:
+            assert flat.selected_clients == [] and shard.selected_clients == [] and flat.client_scores == []
+            flat.publish()
+            shard.publish()
+        assert tuple(a.shape) == (P,) and torch.equal(a, b)
+        assert torch.equal(flat.distances, shard.distances)
+        assert len(flat.selected_clients) == nsel and flat.selected_clients == shard.selected_clients
+        assert len(flat.rejected_clients) == K - nsel and flat.rejected_clients == shard.rejected_clients
+        assert flat.client_scores == shard.client_scores and len(flat.client_scores) == K
+
+
 # ---------------- 2 ranks on one GPU (gloo) vs 1 rank ----------------
 
 def _free_port():
