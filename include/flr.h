@@ -391,6 +391,89 @@ int flr_minmax_rows(float* X, int64_t K, int64_t P, int64_t ldx, int64_t nmal,
                     double* gamma_out, double* stats_out, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ---- model replacement: the scaled backdoor (Bagdasaryan et al., AISTATS 2020)
+ * "How To Backdoor Federated Learning": the attackers (rows 0..f-1, trained on
+ * triggered data) boost their update so that it survives the average,
+ *   x_i <- g + gamma_i * (x_i - g),      g the model the round trained from,
+ * and shrink it back under the bound the server enforces (Sun et al. 2019, "Can
+ * You Really Backdoor Federated Learning?"; Wang et al., NeurIPS 2020; the
+ * "constrain" half of constrain-and-scale).  No reference counterpart.  Two
+ * calls, each enqueued on the stream with no host synchronisation; nothing is
+ * written on an error.
+ *
+ * flr_replace_strength: gamma_i of the f attackers from the round's own matrix.
+ * One workgroup, a lane per client; all arithmetic fp64, every operation rounded
+ * on its own (no FMA), only + - * / sqrt, in this order.
+ *   e_j: norms[j] = ||x_j - g|| (flr_row_norms with the center g); in distance
+ *     mode norms may be NULL, then e_j = sqrt(G_jj).
+ *   G: the centered Gram matrix flr_rows_gram(X, center = g), G_jk = <x_j - g,
+ *     x_k - g>; read in distance mode only (NULL otherwise), taken as symmetric
+ *     (the kernel reads G_ji for G_ij).
+ *   The benign rows are f..K-1, nb = K - f of them.
+ *   FLR_REPLACE_NONE: gamma_i = boost, status 0; norms and G are not read.
+ *   FLR_REPLACE_NORM: gamma_i = min(boost, rho * B / e_i), B a statistic of the
+ *     benign e_j:
+ *       FLR_REPLACE_MEDIAN  numpy's median: the sorted values' middle one, or
+ *                           (lo + hi) / 2 of the two middle ones
+ *       FLR_REPLACE_MAX     the largest
+ *       FLR_REPLACE_MEAN    ((e_f + e_f+1) + ...) + e_K-1, rows ascending, / nb
+ *     a NaN among the benign e_j makes B NaN (+inf is a value like any other).
+ *       bound = rho * B
+ *       e_i == 0:                gamma_i = boost            status 0
+ *       boost * e_i <= bound:    gamma_i = boost            status 0
+ *       else:                    gamma_i = bound / e_i      status 1
+ *   FLR_REPLACE_DISTANCE: the largest gamma_i <= boost with
+ *     ||g + gamma_i (x_i - g) - x_j|| <= rho * max_{j,k benign} ||x_j - x_k|| for
+ *     every benign j — the Min-Max criterion on each attacker's own direction.
+ *       D2 = max(0, max_{j<k benign} ((G_jj + G_kk) - 2 * G_jk)), a NaN term kept
+ *       b2 = (rho * rho) * D2                                 (B = D2 here)
+ *       per attacker i, a = G_ii, and benign j, b = G_ij, c = G_jj - b2:
+ *         disc = b * b - a * c            (two products, one subtraction)
+ *         gamma_ij = (b + sqrt(max(0, disc))) / a
+ *           (the larger root of a t^2 - 2 b t + c = 0; disc < 0: no t meets row
+ *           j's bound, gamma_ij = b / a is the point closest to x_j)
+ *       m = min_j gamma_ij, a NaN once seen kept
+ *       gamma_i = min(boost, max(0, m))
+ *       status 2 when some disc < 0 or m < 0 (no gamma >= 0 meets every bound),
+ *       else 1 when gamma_i < boost, else 0.   a == 0: gamma_i = boost, status 0.
+ *   Not finite: B not finite sets every gamma_i = 1, every status 3 and bit 0 of
+ *     flags.  Otherwise an attacker with e_i not finite (distance mode: G_ii not
+ *     finite too) or a NaN gamma_i gets gamma_i = 1, status 3, and sets bit 1.
+ *   gamma32_i = (float)gamma64_i.
+ * gamma64: device fp64 [f]; gamma32: device fp32 [f]; status: device int32 [f]
+ * (0 boost-limited, 1 bound-limited, 2 infeasible: the closest point taken, 3 left
+ * alone: gamma = 1); flags: device int32 [1].  Bytes: norms once; distance mode
+ * reads the benign block of G once and the attackers' columns once (L2).
+ * FLR_ERR_ARG: null gamma64, gamma32, status or flags; norms NULL in norm mode; G
+ * NULL in distance mode; f < 1; f >= K; boost or rho not a finite number > 0; mode
+ * or stat outside their values; distance mode with K - f < 2.
+ * FLR_ERR_UNSUPPORTED: K > 1024.
+ *
+ * flr_scale_rows_from, in place, rows i < n: three separately rounded fp32
+ * operations per element (no FMA),
+ *   X_ip = fl(c_p + fl(fl(X_ip - c_p) * gamma_i))
+ * A row with gamma_i == 1 or a NaN gamma_i is neither read nor written (boost = 1
+ * is the plain backdoor bit for bit).  Rows >= n and columns [P, ldx) are never
+ * touched.  center: device fp32 [P], not inside X; gamma32: device fp32 [n].  A
+ * workgroup owns 256 lanes of one row, a lane one float4 of coordinates (or one
+ * coordinate: X or center not 16-byte aligned, or ldx % 4 != 0; the same bits).
+ * n == 0: FLR_OK, nothing done.
+ * Bytes moved: 2 * (rows with gamma != 1) * P * 4 + P * 4 (the center is read once
+ * per scaled row; past the first the caches serve it).
+ * FLR_ERR_ARG: null X, center or gamma32; K < 1; P < 1; ldx < P; n < 0; n > K.
+ * FLR_ERR_UNSUPPORTED: n > 65535. */
+#define FLR_REPLACE_NONE 0
+#define FLR_REPLACE_NORM 1
+#define FLR_REPLACE_DISTANCE 2
+#define FLR_REPLACE_MEDIAN 0
+#define FLR_REPLACE_MAX 1
+#define FLR_REPLACE_MEAN 2
+int flr_replace_strength(const double* norms, const double* G, int64_t K, int64_t f,
+                         double boost, int mode, int stat, double rho, double* gamma64,
+                         float* gamma32, int32_t* status, int32_t* flags, void* stream);
+int flr_scale_rows_from(float* X, int64_t K, int64_t P, int64_t ldx, const float* center,
+                        const float* gamma32 /* device [n] */, int64_t n, void* stream);
+
 /* ---- centered clipping (Karimireddy, He, Jaggi, ICML 2021) ---------------
  * "Learning from History for Byzantine Robust Optimization": from the previous
  * global model v0, iters times

@@ -81,6 +81,9 @@ SIGNATURES = {
     "flr_minmax_workspace": (_size_t, [_i64, _i64, _i64]),
     "flr_minmax_rows": (_int, [_c_void_p, _i64, _i64, _i64, _i64, _int, _int, _c_void_p, _c_void_p, _c_void_p,
                                _c_void_p, _size_t, _c_void_p]),
+    "flr_replace_strength": (_int, [_c_void_p, _c_void_p, _i64, _i64, ctypes.c_double, _int, _int, ctypes.c_double,
+                                    _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "flr_scale_rows_from": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _i64, _c_void_p]),
     "flr_centered_clip_workspace": (_size_t, [_i64, _i64]),
     "flr_centered_clip": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, ctypes.c_float, _i64, _c_void_p, _c_void_p,
                                  _c_void_p, _c_void_p, _c_void_p, _size_t, _c_void_p]),

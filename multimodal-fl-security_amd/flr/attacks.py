@@ -32,6 +32,17 @@
   agnostic, the strength computed from the round's own matrix instead of
   guessed per defense; not in the reference.  One flr_minmax_rows call in the
   same slot (min_max_, min_sum_); it needs whole rows.
+* model replacement — "How To Backdoor Federated Learning" (Bagdasaryan et al.,
+  AISTATS 2020): the backdoor above, boosted.  The attackers train on the
+  triggered data and then submit g + gamma_i * (x_i - g), gamma_i = boost
+  (default K / f, the paper's n / eta at server rate 1 shared by the f
+  attackers) or what is left of it under the server's bound: rho times a
+  statistic of the benign rows' norms (Sun et al. 2019), or rho times the
+  benign rows' largest mutual distance (the Min-Max criterion on each
+  attacker's own direction).  Not in the reference; what norm_bounding,
+  gradient_clipping, dp_sgd, robust_lr, foolsgold and krum are judged by.
+  flr_replace_strength + flr_scale_rows_from in the colluding attacks' slot
+  (model_replacement_).
 """
 from __future__ import annotations
 
@@ -111,6 +122,57 @@ def min_sum_(X, f: int, perturb: str = "std", global_flat: Optional[torch.Tensor
     larger than the largest sum of squared distances from one benign row to the
     others."""
     return _minmax(X, f, ops.MINMAX_SUM, perturb, global_flat)
+
+
+STEALTH = {"none": ops.REPLACE_NONE, "norm": ops.REPLACE_NORM, "distance": ops.REPLACE_DISTANCE}
+STATS = {"median": ops.REPLACE_MEDIAN, "max": ops.REPLACE_MAX, "mean": ops.REPLACE_MEAN}
+
+
+def replacement_config(K: int, f: int, boost=None, stealth: str = "none", stat: str = "median",
+                       rho=1.0) -> Tuple[float, int, int, float]:
+    """(boost, mode, stat, rho) of model_replacement_ checked on the host: the
+    names known, boost (None: K / f) and rho finite numbers > 0, 1 <= f < K, and
+    two benign rows for the distance bound."""
+    if stealth not in STEALTH:
+        raise ValueError(f"unknown stealth {stealth!r} (one of {', '.join(STEALTH)})")
+    if stat not in STATS:
+        raise ValueError(f"unknown stat {stat!r} (one of {', '.join(STATS)})")
+    if not 1 <= f < K:
+        raise ValueError(f"model replacement needs 1 <= f < K (got f = {f}, K = {K})")
+    if stealth == "distance" and K - f < 2:
+        raise ValueError(f"stealth 'distance' needs two benign rows (got K - f = {K - f})")
+    boost = K / f if boost is None else ops._positive_finite(boost, "boost")
+    return boost, STEALTH[stealth], STATS[stat], ops._positive_finite(rho, "rho")
+
+
+def replace_rows_(M: torch.Tensor, f: int, g: torch.Tensor, boost: float, mode: int, stat: int, rho: float):
+    """model_replacement_ on a matrix with replacement_config's checked values
+    (the round engine's call): the statistic pass its mode needs, the strengths,
+    the scale; (gamma, status, flags)."""
+    norms = ops.row_norms(M, center=g) if mode == ops.REPLACE_NORM else None
+    G = ops.rows_gram(M, center=g) if mode == ops.REPLACE_DISTANCE else None
+    gamma, gamma32, status, flags = ops.replace_strength(norms, G, f, boost, mode, stat, rho, K=M.shape[0],
+                                                         device=M.device)
+    ops.scale_rows_from(M, g, gamma32)
+    return gamma, status, flags
+
+
+def model_replacement_(X, f: int, global_flat: torch.Tensor, boost: Optional[float] = None, stealth: str = "none",
+                       stat: str = "median", rho: float = 1.0):
+    """In place on a float32 device matrix or a ClientMatrix whose rows 0..f-1
+    were trained on the backdoor's data: row i <- g + gamma_i * (x_i - g), g =
+    global_flat, the model the round trained from.  gamma_i = boost (None: K /
+    f) under stealth "none"; "norm": min(boost, rho * B / ||x_i - g||), B the
+    stat ("median", "max" or "mean") of the benign rows' ||x_j - g||;
+    "distance": the largest gamma_i <= boost that keeps the row within rho
+    times the benign rows' largest mutual distance of every benign row.  The
+    strengths are solved on the device from the matrix itself: no host round
+    trip.  Returns (gamma float64 [f], status int32 [f] — 0 boost-limited, 1
+    bound-limited, 2 infeasible (the closest point), 3 left alone —, flags
+    int32 [1]: bit 0 a non-finite benign statistic (every row left alone), bit
+    1 a non-finite attacker) as device tensors."""
+    M = X if isinstance(X, torch.Tensor) else X.X
+    return replace_rows_(M, int(f), global_flat, *replacement_config(M.shape[0], int(f), boost, stealth, stat, rho))
 
 
 class Backdoor:

@@ -297,6 +297,92 @@ def minmax_rows(X: torch.Tensor, nmal: int, objective: int, perturb: int, global
             ws[sig:sig + 4 * P].view(torch.float32).clone())
 
 
+REPLACE_NONE, REPLACE_NORM, REPLACE_DISTANCE = 0, 1, 2  # FLR_REPLACE_* (mode)
+REPLACE_MEDIAN, REPLACE_MAX, REPLACE_MEAN = 0, 1, 2      # FLR_REPLACE_* (stat)
+REPLACE_MAX_CLIENTS = 1024  # flr_replace_strength's limit
+
+
+def _positive_finite(value, name: str) -> float:
+    """value as a float, a finite number > 0 (a bool or a string is not one)."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not 0.0 < float(value) < float("inf"):
+        raise ValueError(f"{name} must be a finite number > 0, got {value!r}")
+    return float(value)
+
+
+def replace_strength(norms: Optional[torch.Tensor], G: Optional[torch.Tensor], f: int, boost: float,
+                     mode: int = REPLACE_NONE, stat: int = REPLACE_MEDIAN, rho: float = 1.0,
+                     K: Optional[int] = None, device=None):
+    """Model replacement's strengths (flr_replace_strength; the arithmetic in
+    include/flr.h): gamma_i of the attackers 0..f-1, boost cut back to rho times
+    a statistic of the benign rows' norms (REPLACE_NORM: stat REPLACE_MEDIAN /
+    REPLACE_MAX / REPLACE_MEAN) or to rho times their largest mutual distance
+    (REPLACE_DISTANCE).  norms: float64 [K], row_norms(X, center=g) (None in
+    REPLACE_NONE, optional in REPLACE_DISTANCE); G: float64 [K, K],
+    rows_gram(X, center=g) (REPLACE_DISTANCE only).  K and device are taken from
+    norms or G, or given (REPLACE_NONE with neither).  Returns (gamma64 float64
+    [f], gamma32 float32 [f], status int32 [f] — 0 boost-limited, 1
+    bound-limited, 2 infeasible, 3 left alone —, flags int32 [1]: bit 0 a
+    non-finite benign statistic, bit 1 a non-finite attacker) as device tensors;
+    no host synchronisation."""
+    f, mode, stat = int(f), int(mode), int(stat)
+    boost, rho = _positive_finite(boost, "boost"), _positive_finite(rho, "rho")
+    if mode not in (REPLACE_NONE, REPLACE_NORM, REPLACE_DISTANCE):
+        raise ValueError(f"unknown replace_strength mode {mode}")
+    if stat not in (REPLACE_MEDIAN, REPLACE_MAX, REPLACE_MEAN):
+        raise ValueError(f"unknown replace_strength stat {stat}")
+    for name, t in (("norms", norms), ("G", G)):
+        if t is not None:
+            if not isinstance(t, torch.Tensor) or not t.is_cuda:
+                raise RuntimeError(f"{name} must be a CUDA/HIP tensor (the engine has no CPU path)")
+            K = t.shape[0] if K is None else K
+            device = t.device if device is None else device
+    if K is None or device is None:
+        raise ValueError("replace_strength needs norms, G, or K and device")
+    K, device = int(K), torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("replace_strength runs on a CUDA/HIP device (the engine has no CPU path)")
+    if not 1 <= f < K:
+        raise ValueError(f"replace_strength needs 1 <= f < K (got f = {f}, K = {K})")
+    if K > REPLACE_MAX_CLIENTS:
+        raise ValueError(f"replace_strength handles at most {REPLACE_MAX_CLIENTS} clients, got {K}")
+    if norms is not None:
+        _check_vector(norms, K, device, "norms", torch.float64)
+    if G is not None and (G.device != device or G.dtype != torch.float64 or tuple(G.shape) != (K, K)
+                          or not G.is_contiguous()):
+        raise ValueError(f"G must be a contiguous float64 [{K}, {K}] matrix on {device}")
+    if mode == REPLACE_NORM and norms is None:
+        raise ValueError("REPLACE_NORM needs norms")
+    if mode == REPLACE_DISTANCE:
+        if G is None:
+            raise ValueError("REPLACE_DISTANCE needs G")
+        if K - f < 2:
+            raise ValueError(f"REPLACE_DISTANCE needs two benign rows (got K - f = {K - f})")
+    gamma64 = torch.empty(f, dtype=torch.float64, device=device)
+    gamma32 = torch.empty(f, dtype=torch.float32, device=device)
+    status = torch.empty(f, dtype=torch.int32, device=device)
+    flags = torch.empty(1, dtype=torch.int32, device=device)
+    _capi.call("flr_replace_strength", _ptr(norms), _ptr(G), K, f, boost, mode, stat, rho, gamma64.data_ptr(),
+               gamma32.data_ptr(), status.data_ptr(), flags.data_ptr(), _stream(gamma64))
+    return gamma64, gamma32, status, flags
+
+
+def scale_rows_from(X: torch.Tensor, center: torch.Tensor, gamma32: torch.Tensor) -> torch.Tensor:
+    """In place (flr_scale_rows_from): rows i < n = len(gamma32) of X <- center +
+    (X_i - center) * gamma32[i], three separately rounded fp32 operations; a row
+    with gamma32[i] == 1 or NaN is neither read nor written.  center: float32
+    [P], gamma32: float32 [n], n <= K, on X's device.  Returns X."""
+    K, P, ldx = _check_matrix(X)
+    if K < 1 or P < 1:
+        raise ValueError(f"scale_rows_from needs K >= 1 and P >= 1, got {K} x {P}")
+    _check_vector(center, P, X.device, "center")
+    n = gamma32.numel() if isinstance(gamma32, torch.Tensor) else -1
+    if n > K:
+        raise ValueError(f"gamma32 has {n} entries for {K} rows")
+    _check_vector(gamma32, n, X.device, "gamma32")
+    _capi.call("flr_scale_rows_from", X.data_ptr(), K, P, ldx, center.data_ptr(), gamma32.data_ptr(), n, _stream(X))
+    return X
+
+
 def centered_clip(X: torch.Tensor, v0: torch.Tensor, tau: float, iters: int, out: Optional[torch.Tensor] = None,
                   diagnostics: bool = False):
     """Centered clipping (flr_centered_clip): from v0, iters times

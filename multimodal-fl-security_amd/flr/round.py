@@ -28,7 +28,7 @@ import torch
 from . import _capi
 from . import dist as fdist
 from . import ops
-from .attacks import PERTURBATIONS, Backdoor, alie_z, poison_batches_
+from .attacks import PERTURBATIONS, Backdoor, alie_z, poison_batches_, replace_rows_, replacement_config
 from .defenses import get_defense
 from .defenses.krum import DeadTaps
 from .matrix import ClientMatrix
@@ -37,7 +37,7 @@ from .models.multimodal import ModelSpec, model_class, param_layout
 from .train import ClientBatchTrainer, TrainConfig, make_dropout_masks, synthetic_batches
 
 
-ATTACKS = ("sign_flip", "backdoor", "none", "alie", "ipm", "min_max", "min_sum")
+ATTACKS = ("sign_flip", "backdoor", "none", "alie", "ipm", "min_max", "min_sum", "model_replacement")
 
 
 @dataclass
@@ -48,7 +48,8 @@ class RoundConfig:
     defense_cfg: Dict = field(default_factory=dict)
     # "sign_flip" (model_poisoning.py:274-276) | "backdoor" | "none" | "alie" | "ipm" (the colluding attacks of
     # flr.attacks: one flr_collude_rows pass between the exchange and the defense) | "min_max" | "min_sum" (one
-    # flr_minmax_rows call in the same slot; whole rows: the all-gather exchange unless world == 1)
+    # flr_minmax_rows call in the same slot; whole rows: the all-gather exchange unless world == 1) |
+    # "model_replacement" (the backdoor's data, then the attackers' rows boosted about the global model in that slot)
     attack: str = "sign_flip"
     num_attackers: int = 25              # f = int(0.2 K), clients 0..f-1 (experiment_matrix.py:67-68)
     seed: int = 42                       # run_experiments.py:43
@@ -63,7 +64,9 @@ class RoundConfig:
     # False keeps device errors loud at world 1 too
     fallback_device_errors: bool = True
     # "z" (alie; default alie_z(K, f)), "epsilon" (ipm; default 0.5), "perturb" (min_max / min_sum: "std" (default) |
-    # "sign" | "unit", the direction of flr.attacks.min_max_)
+    # "sign" | "unit", the direction of flr.attacks.min_max_); model_replacement: "boost" (default num_clients /
+    # num_attackers), "stealth" ("none" (default) | "norm" | "distance"), "stat" (norm: "median" (default) | "max" |
+    # "mean"), "rho" (default 1.0), the arguments of flr.attacks.model_replacement_
     attack_cfg: Dict = field(default_factory=dict)
 
 
@@ -94,6 +97,8 @@ class RoundEngine:
         # attack_gamma: the last round's strength, a float64 device scalar (experiment logs)
         self._minmax = None
         self.attack_gamma: Optional[torch.Tensor] = None
+        self.attack_status: Optional[torch.Tensor] = None  # model replacement: int32 [f] and int32 [1]
+        self.attack_flags: Optional[torch.Tensor] = None   # (flr.attacks.model_replacement_)
         if rcfg.attack in ("min_max", "min_sum"):
             K, f = rcfg.num_clients, rcfg.num_attackers
             if not 1 <= f < K:
@@ -106,6 +111,24 @@ class RoundEngine:
                                  "coordinate-wise statistic): use exchange='allgather' (a rank's all-to-all slice "
                                  "is the whole matrix only at world 1)")
             self._minmax = (ops.MINMAX_MAX if rcfg.attack == "min_max" else ops.MINMAX_SUM, PERTURBATIONS[perturb])
+        # model replacement: (boost, mode, stat, rho) of the flr_replace_strength call per round; attack_gamma is
+        # then the float64 [f] vector of the attackers' strengths
+        self._replace = None
+        self._replace_whole_rows = False
+        if rcfg.attack == "model_replacement":
+            unknown = set(rcfg.attack_cfg) - {"boost", "stealth", "stat", "rho"}
+            if unknown:
+                raise ValueError(f"attack_cfg keys {sorted(unknown)} are not model_replacement's "
+                                 "(boost, stealth, stat, rho)")
+            self._replace = replacement_config(rcfg.num_clients, rcfg.num_attackers, rcfg.attack_cfg.get("boost"),
+                                               rcfg.attack_cfg.get("stealth", "none"),
+                                               rcfg.attack_cfg.get("stat", "median"), rcfg.attack_cfg.get("rho", 1.0))
+            self._replace_whole_rows = self._replace[1] != ops.REPLACE_NONE  # "auto" takes the all-gather below
+            if self._replace_whole_rows and rcfg.exchange == "alltoall" and world > 1:
+                raise ValueError(f"model_replacement with stealth {rcfg.attack_cfg['stealth']!r} needs whole client "
+                                 "rows (row norms and distances, not a coordinate-wise statistic): use "
+                                 "exchange='allgather' (a rank's all-to-all slice is the whole matrix only at "
+                                 "world 1)")
         defer = os.environ.get("FLR_DEFER_DEAD", "2")
         if defer == "1":  # loud: an old A/B script must not report numbers for another mode
             raise ValueError("FLR_DEFER_DEAD=1 (the dead-tap fill on a side stream beside the Krum chains) was "
@@ -139,7 +162,7 @@ class RoundEngine:
         mode = rcfg.exchange
         if mode == "auto":
             mode = "alltoall" if (self.defense.supports_sharded and PW_SLICES % world == 0
-                                  and self._minmax is None) else "allgather"
+                                  and self._minmax is None and not self._replace_whole_rows) else "allgather"
         if mode not in ("alltoall", "allgather"):
             raise ValueError(f"unknown exchange mode {rcfg.exchange!r}")
         if mode == "alltoall" and not self.defense.supports_sharded:
@@ -152,7 +175,8 @@ class RoundEngine:
         self.batches = synthetic_batches(spec, steps, range(self.lo, self.hi), rcfg.batch, self.device)
         self.masks = make_dropout_masks(spec, steps, range(self.lo, self.hi), rcfg.batch, self.device,
                                         seed=rcfg.seed + 7919)
-        if rcfg.attack == "backdoor":  # data poisoning of the malicious clients (run_experiments.py:173-175)
+        # data poisoning of the malicious clients (run_experiments.py:173-175)
+        if rcfg.attack in ("backdoor", "model_replacement"):
             cols = [c - self.lo for c in range(self.lo, min(self.hi, rcfg.num_attackers))]
             poison_batches_(self.batches, cols, Backdoor(image_size=(spec.image_size, spec.image_size)))
         self.num_examples = [steps * rcfg.batch] * K  # len(client dataset) (run_experiments.py:240)
@@ -166,9 +190,10 @@ class RoundEngine:
         # the trainer's coordinate order, written by the last optimizer step;
         # gtrain is the global model in that order (FLR_ORDER=torch: off)
         # Min-Max / Min-Sum read the round's global model beside the matrix: torch
-        # order, where global_flat lines up with the columns
+        # order, where global_flat lines up with the columns (model replacement likewise)
         self.train_order = (getattr(self.defense, "order_free", False) and not self._wants_global
-                            and self._minmax is None and os.environ.get("FLR_ORDER", "train") != "torch")
+                            and self._minmax is None and self._replace is None
+                            and os.environ.get("FLR_ORDER", "train") != "torch")
         bounds = None
         if self.train_order and getattr(self.defense, "needs_tap_blocks", False):
             # the reference-exact distances read the training-order matrix,
@@ -374,7 +399,8 @@ class RoundEngine:
         self.fallback_error = None
         if self.exchange == "alltoall":
             cs = self._slice = self.xchg.exchange(self.trainer.X.data)
-            self._apply_collusion(cs.X)  # coordinate-wise: this rank's slice needs no other
+            # coordinate-wise: this rank's slice needs no other
+            self._apply_collusion(cs.X, self.global_flat[cs.begin:cs.end])
             if self._wants_global:  # the robust learning rate: global_flat is overwritten below
                 kw["global_flat"] = self.global_flat[cs.begin:cs.end].clone()
             try:
@@ -393,15 +419,21 @@ class RoundEngine:
             agg = self._fallback(e, self._full.X)
         return self._publish(agg)
 
-    def _apply_collusion(self, X: torch.Tensor) -> None:
+    def _apply_collusion(self, X: torch.Tensor, g: Optional[torch.Tensor] = None) -> None:
         """attack "alie" / "ipm" / "min_max" / "min_sum": the attackers (clients
         0..f-1, who trained honestly) replace their rows of the exchanged matrix
         by the colluding vector, computed from the benign rows — after the
-        exchange, before the defense, outside the captured training graph."""
+        exchange, before the defense, outside the captured training graph.
+        "model_replacement": they boost their own (backdoored) rows about the
+        global model; g is global_flat, or its slice beside a rank's coordinate
+        range (stealth "none" alone runs there: it is coordinate-wise)."""
         if self._collude is not None:
             ops.collude_rows(X, self.rcfg.num_attackers, *self._collude)
         if self._minmax is not None:  # global_flat: still the model this round trained from
             self.attack_gamma = ops.minmax_rows(X, self.rcfg.num_attackers, *self._minmax, self.global_flat)
+        if self._replace is not None:
+            self.attack_gamma, self.attack_status, self.attack_flags = replace_rows_(
+                X, self.rcfg.num_attackers, self.global_flat if g is None else g, *self._replace)
 
     def _fallback(self, err: Exception, X: torch.Tensor) -> torch.Tensor:
         """robust_server.py:120-122: a failing defense falls back to FedAvg
