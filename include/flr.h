@@ -474,6 +474,141 @@ int flr_replace_strength(const double* norms, const double* G, int64_t K, int64_
 int flr_scale_rows_from(float* X, int64_t K, int64_t P, int64_t ldx, const float* center,
                         const float* gamma32 /* device [n] */, int64_t n, void* stream);
 
+/* ---- Fang et al.'s full-knowledge attacks on Krum and on the trimmed mean -----
+ * Fang, Cao, Jia, Gong, "Local Model Poisoning Attacks to Byzantine-Robust
+ * Federated Learning", USENIX Security 2020: the attacks written against one
+ * aggregation rule each, the baseline Min-Max / Min-Sum are measured against.  No
+ * reference counterpart.  In place on the client matrix, as flr_collude_rows:
+ * rows [0, nmal) are the attackers and are overwritten, rows [nmal, K) are benign
+ * and only read, nb = K - nmal; columns [P, ldx) are never touched.  The rows are
+ * model weights; `global` (device fp32 [P]) is the model g the round trained
+ * from.  Every call is enqueued on the stream, no host synchronisation; nothing
+ * is written on an error.
+ *
+ * The directed deviation, shared by both: mu is flr_collude_rows' mean_out (its
+ * arithmetic, its bits) and, per coordinate, fp32,
+ *   t = fl(mu - g);  s = sign(t), sign(0) = 0, sign(NaN) = NaN
+ * the FLR_PERTURB_SIGN convention.  (The paper maps 0 to -1; here a coordinate
+ * the benign clients did not move is not attacked.)
+ *
+ * flr_fang_krum_rows, the Krum attack: every attacker submits m = g - lambda * s,
+ * all nmal rows identical (the paper's epsilon-ball around the first is dropped,
+ * as in the authors' later code), lambda the largest of lambda0 * 2^-t, t = 0, 1,
+ * ..., for which Krum picks an attacker's row — flr_krum_select's rule: the score
+ * is the sum of the K - f - 2 smallest distances to the others, the smallest
+ * score wins, ties to the lower index (the attackers have the lower indices).
+ * The paper probes each lambda with a Krum over the attacked matrix; here the
+ * probe is closed: with u_i = x_i - g over the benign rows, G_ij = <u_i, u_j>,
+ * b_i = <s, u_i>, c = <s, s>,  ||m - x_i||^2 = G_ii + 2 lambda b_i + lambda^2 c,
+ * and the benign rows' mutual distances do not depend on lambda.  Stages:
+ *   1. mu: as above, no row written.
+ *   2. G: flr_rows_gram on the benign rows with center g, nb x nb fp64.
+ *   3. b_i = sum_k s_k * fl(x_ik - g_k), c = sum_k s_k * s_k: each product exact
+ *      in fp64, each sum a fixed-order fp64 sum whose order is the kernel's own (a
+ *      function of K, P, ldx and the pointers' 16-B alignment alone: run-to-run
+ *      identical bits, no float atomics), accurate to about P * 2^-53 relative,
+ *      not bit-defined.  The benign rows are read once; s is stored beside mu.
+ *   4. flr_fang_krum_strength (a call of its own: G, b, c device inputs).  All
+ *      arithmetic fp64, every operation rounded on its own (no FMA), only + - * /
+ *      sqrt, in this order; max0(x) is 0 for x < 0, else x (a NaN stays):
+ *        m = K - f - 2;  na = K - 2f - 1;  e_i = G_ii             (f = nmal)
+ *        D_ij = sqrt(max0((e_i + e_j) - 2 * G_ij))  for j != i
+ *        r_i = those nb - 1 values in ascending order, NaN last (a kernel of a
+ *          workgroup per row, into the workspace)
+ *        then one workgroup, a lane per benign row:
+ *        T_i = sequential sum from 0.0 of r_i[0 .. m-1];  T = min_i T_i, a NaN kept
+ *        E = max_i sqrt(e_i), a NaN kept;  rc = sqrt(c)
+ *        any NaN among e_i, b_i, c, T:  lambda = NaN, status 3
+ *        else c == 0:                   lambda = 0,   status 2   (g == mu: no direction)
+ *        else lambda0 = T / ((double)na * rc) + E / rc
+ *          (the paper's Theorem 1 with its m -> K, c -> f, and sqrt(d) -> rc
+ *          because s may hold zeros);  lambda0 not finite: lambda = NaN, status 3
+ *        else for t = 0, 1, ...: lambda = lambda0 halved t times
+ *          lambda <= threshold:  stop, status 1, this lambda (the search failed;
+ *            with f = 1 it usually does, as the paper says: one crafted model has
+ *            no zero-distance companion)
+ *          d_i = sqrt(max0((e_i + (2 * lambda) * b_i) + (lambda * lambda) * c))
+ *          S_att = sequential sum from 0.0, ascending, of the na smallest d_i (an
+ *            attacker's score: its f - 1 companions are at distance 0)
+ *          S_i = sequential sum from 0.0, ascending, of the m smallest of the
+ *            multiset r_i and f copies of d_i (NaN last)
+ *          S_min = min_i S_i, a NaN kept
+ *          S_att <= S_min:  stop, status 0, this lambda
+ *      lambda64: device fp64 [1]; lambda32 = (float)lambda64: device fp32 [1];
+ *      info: device int32 [2], status (0 found, 1 threshold reached, 2 no
+ *      direction, 3 not finite) and t (0 for status 2 and 3); stats_out: optional
+ *      device fp64 [5]: lambda0, T, E, the last probe's S_att and S_min (NaN where
+ *      not computed).  G: device fp64 nb x nb (the benign rows alone), b: device
+ *      fp64 [nb], c: device fp64 [1].  Workspace:
+ *      flr_fang_krum_strength_workspace(K, nmal) bytes (the sorted rows; 0 for
+ *      rejected arguments), 256-byte aligned.
+ *      FLR_ERR_ARG: a null G, b, c, lambda64, lambda32 or info; nmal < 1; threshold
+ *      not a finite number > 0.  FLR_ERR_KRUM_N: K < 2 nmal + 3, Krum's own
+ *      condition.  FLR_ERR_UNSUPPORTED: nb > 1024.  FLR_ERR_WORKSPACE.
+ *   5. the rows, two separately rounded fp32 ops per element (no FMA):
+ *        out_k = fl(g_k - fl(lambda32 * s_k))
+ *      A NaN lambda writes nothing: the rows stay as they were.  A lane owns one
+ *      float4 of coordinates, or one coordinate (X or global not 16-byte aligned,
+ *      or ldx % 4 != 0): the same bits.
+ * lambda_out: optional device fp64 [1]; info_out: optional device int32 [2];
+ * stats_out: optional device fp64 [nb + 6]: b_i [nb], c, then the strength call's
+ * five; gram_out: optional device fp64 nb x nb, G.  Workspace:
+ * flr_fang_krum_workspace(K, P, nmal) bytes (0 for arguments the call rejects),
+ * 256-byte aligned: mu, s, G, flr_rows_gram's workspace, the sorted rows, the
+ * partial sums.  After the call its first P floats hold mu and the P floats at
+ * byte offset (4*P + 255) / 256 * 256 hold s.
+ * Bytes moved: 3 * nb * P * 4 read (mean, Gram, statistics) + nmal * P * 4
+ * written, as flr_minmax_rows; not timed yet.
+ * FLR_ERR_ARG: null X or global, K < 2, nmal < 1, nmal >= K, P < 1, ldx < P,
+ * threshold not a finite number > 0.  FLR_ERR_KRUM_N: K < 2 nmal + 3.
+ * FLR_ERR_UNSUPPORTED: nb > 1024 (flr_rows_gram's row limit, the one-workgroup
+ * solver's too).  FLR_ERR_WORKSPACE: workspace null, too small or not 256-byte
+ * aligned.
+ *
+ * flr_fang_trim_rows, the trimmed-mean / median attack: per coordinate the
+ * attackers sit just beyond the benign extreme on the side opposite s, each at a
+ * point of its own drawn between two bounds.  One pass reads the benign rows and
+ * writes the attackers' rows.  Per coordinate k, fp32, every operation rounded on
+ * its own, the benign rows in ascending order:
+ *   mu, s: as above.   mn = mx = the first benign value; then per row
+ *   mn = x < mn ? x : mn,  mx = x > mx ? x : mx.
+ *   s > 0:  mn > 0: (near, far) = (mn, mn / b);  else (mn, mn * b)
+ *   s < 0:  mx > 0: (near, far) = (mx, mx * b);  else (mx, mx / b)
+ *   attacker i:  out = fl(near + fl(u_ik * fl(far - near)))
+ *   s == 0: every attacker gets mu_k.   s NaN (a NaN in a benign row, or in g):
+ *   every attacker gets fl(mu_k - g_k), a NaN — in that coordinate and no other.
+ *   u_ik = (w >> 8) * 2^-24 in [0, 1), w word 0 of Philox4x32-10 (Salmon, Moraes,
+ *   Dror, Shaw, "Parallel Random Numbers: As Easy as 1, 2, 3", SC 2011) with key
+ *   (seed & 0xffffffff, seed >> 32) and counter (c & 0xffffffff, c >> 32, i,
+ *   draw_stream), c = col0 + k.  Ten rounds; round r = 0..9 on counter (c0, c1,
+ *   c2, c3) with key (k0, k1) bumped by (0x9E3779B9, 0xBB67AE85) mod 2^32 before
+ *   every round but the first:
+ *     p0 = 0xD2511F53 * c0, p1 = 0xCD9E8D57 * c2          (64-bit products)
+ *     (c0, c1, c2, c3) <- (hi(p1) ^ c1 ^ k0, lo(p1), hi(p0) ^ c3 ^ k1, lo(p0))
+ *   No device RNG library is linked.
+ * b: fp32, finite, > 1 (the paper uses 2).  col0 >= 0: the global index of column
+ * 0, so a column range of X called with its own col0 (same ldx) gives that range
+ * of the whole-matrix call, bit for bit.  draw_stream: the round index.  Any K
+ * with 1 <= nmal < K; no workspace.  A lane owns one float4 of coordinates, or one
+ * coordinate (as above: the same bits).
+ * Bytes moved: nb * P * 4 + P * 4 read, nmal * P * 4 written.
+ * FLR_ERR_ARG: null X or global, K < 2, nmal < 1, nmal >= K, P < 1, ldx < P, b not
+ * a finite number > 1, col0 < 0 or col0 + P past 2^63 - 1. */
+#define FLR_FANG_THRESHOLD 1e-5 /* the paper's */
+size_t flr_fang_krum_strength_workspace(int64_t K, int64_t nmal);
+int flr_fang_krum_strength(const double* G, const double* b, const double* c, int64_t K,
+                           int64_t nmal, double threshold, double* lambda64, float* lambda32,
+                           int32_t* info, double* stats_out, void* workspace,
+                           size_t workspace_bytes, void* stream);
+size_t flr_fang_krum_workspace(int64_t K, int64_t P, int64_t nmal);
+int flr_fang_krum_rows(float* X, int64_t K, int64_t P, int64_t ldx, int64_t nmal,
+                       const float* global, double threshold, double* lambda_out,
+                       int32_t* info_out, double* stats_out, double* gram_out,
+                       void* workspace, size_t workspace_bytes, void* stream);
+int flr_fang_trim_rows(float* X, int64_t K, int64_t P, int64_t ldx, int64_t nmal,
+                       const float* global, float b, uint64_t seed, uint32_t draw_stream,
+                       int64_t col0, void* stream);
+
 /* ---- centered clipping (Karimireddy, He, Jaggi, ICML 2021) ---------------
  * "Learning from History for Byzantine Robust Optimization": from the previous
  * global model v0, iters times

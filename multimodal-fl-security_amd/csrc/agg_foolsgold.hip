@@ -258,10 +258,6 @@ __global__ __launch_bounds__(THREADS) void gram_reduce_kernel(const double* __re
 
 // ---- flr_foolsgold_weights ----
 
-__device__ __forceinline__ bool finite64(double x) {
-  return ((uint64_t)__double_as_longlong(x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
-
 // cs_ij from g = G_ji (G is symmetric: lane i's loads of column i coalesce).
 __device__ __forceinline__ double cosine(double g, double ni, double nj, bool offdiag) {
   return (offdiag && ni > 0.0 && nj > 0.0) ? g / (ni * nj) : 0.0;

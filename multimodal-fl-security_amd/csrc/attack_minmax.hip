@@ -155,10 +155,6 @@ __global__ void finish_kernel(const double* __restrict__ part, int nb, int64_t n
   stats[i] = s;
 }
 
-// The larger / smaller value, a NaN once seen kept (numpy's max / min).
-__device__ __forceinline__ double nanmax(double m, double v) { return (v > m || v != v) ? v : m; }
-__device__ __forceinline__ double nanmin(double m, double v) { return (v < m || v != v) ? v : m; }
-
 // One workgroup, fp64 (flr.h's operation order).  stats: a[nb], b[nb], c in;
 // R2, S and the bound used out.
 __global__ __launch_bounds__(THREADS) void solve_kernel(const double* __restrict__ D, int nb, int objective,

@@ -28,14 +28,6 @@ constexpr int MAXK = 1024;  // the strength kernel: one lane per client
 constexpr int S_THREADS = 1024;
 constexpr int S_WAVES = S_THREADS / 64;
 
-__device__ __forceinline__ bool finite64(double x) {
-  return ((uint64_t)__double_as_longlong(x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
-}
-
-// The larger / smaller value, a NaN once seen kept (numpy's max / min).
-__device__ __forceinline__ double nanmax(double m, double v) { return (v > m || v != v) ? v : m; }
-__device__ __forceinline__ double nanmin(double m, double v) { return (v < m || v != v) ? v : m; }
-
 // One workgroup, lane t = client t: t < f an attacker, t >= f benign row t - f.
 __global__ __launch_bounds__(S_THREADS) void strength_kernel(const double* __restrict__ norms,
                                                              const double* __restrict__ G, int K, int f, double boost,

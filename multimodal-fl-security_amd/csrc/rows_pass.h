@@ -1,6 +1,6 @@
 // The column pass over a client matrix, shared by the aggregation and attack
 // units (agg_mean, agg_norm, agg_cclip, agg_dnc, agg_foolsgold, agg_rlr,
-// attack_colluding, attack_minmax, attack_replace): a lane owns one float4 of
+// attack_colluding, attack_fang, attack_minmax, attack_replace): a lane owns one float4 of
 // coordinates, or one coordinate, and walks the rows.  What is here has at least
 // two users and takes no flag that says which caller it serves; a unit whose loop
 // has another contract keeps it.
@@ -171,6 +171,15 @@ __device__ __forceinline__ T block_reduce(T v, T* red, Op&& op) {
   for (int w = 1; w < WAVES; ++w) s = op(s, red[w]);
   return s;
 }
+
+// ---- the fp64 statistics' tests ----
+
+__device__ __forceinline__ bool finite64(double x) {
+  return ((uint64_t)__double_as_longlong(x) & 0x7ff0000000000000ull) != 0x7ff0000000000000ull;
+}
+// The larger / smaller value, a NaN once seen kept (numpy's max / min).
+__device__ __forceinline__ double nanmax(double m, double v) { return (v > m || v != v) ? v : m; }
+__device__ __forceinline__ double nanmin(double m, double v) { return (v < m || v != v) ? v : m; }
 
 // ---- the rank count ----
 

@@ -84,6 +84,14 @@ SIGNATURES = {
     "flr_replace_strength": (_int, [_c_void_p, _c_void_p, _i64, _i64, ctypes.c_double, _int, _int, ctypes.c_double,
                                     _c_void_p, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
     "flr_scale_rows_from": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _i64, _c_void_p]),
+    "flr_fang_krum_strength_workspace": (_size_t, [_i64, _i64]),
+    "flr_fang_krum_strength": (_int, [_c_void_p, _c_void_p, _c_void_p, _i64, _i64, ctypes.c_double, _c_void_p,
+                                      _c_void_p, _c_void_p, _c_void_p, _c_void_p, _size_t, _c_void_p]),
+    "flr_fang_krum_workspace": (_size_t, [_i64, _i64, _i64]),
+    "flr_fang_krum_rows": (_int, [_c_void_p, _i64, _i64, _i64, _i64, _c_void_p, ctypes.c_double, _c_void_p, _c_void_p,
+                                  _c_void_p, _c_void_p, _c_void_p, _size_t, _c_void_p]),
+    "flr_fang_trim_rows": (_int, [_c_void_p, _i64, _i64, _i64, _i64, _c_void_p, ctypes.c_float, ctypes.c_uint64,
+                                  ctypes.c_uint32, _i64, _c_void_p]),
     "flr_centered_clip_workspace": (_size_t, [_i64, _i64]),
     "flr_centered_clip": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, ctypes.c_float, _i64, _c_void_p, _c_void_p,
                                  _c_void_p, _c_void_p, _c_void_p, _size_t, _c_void_p]),

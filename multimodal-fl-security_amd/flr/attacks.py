@@ -43,6 +43,20 @@
   gradient_clipping, dp_sgd, robust_lr, foolsgold and krum are judged by.
   flr_replace_strength + flr_scale_rows_from in the colluding attacks' slot
   (model_replacement_).
+* Fang et al.'s attacks — "Local Model Poisoning Attacks to Byzantine-Robust
+  Federated Learning" (Fang, Cao, Jia, Gong, USENIX Security 2020): the two
+  full-knowledge attacks written against one rule each, the baseline Min-Max
+  and Min-Sum measure themselves against; not in the reference.  Both push
+  against s = sign(mu - g), the direction the benign clients moved in.
+  fang_krum_: every attacker submits g - lambda * s, lambda the largest
+  lambda0 * 2^-t for which Krum picks an attacker — what krum and multi_krum
+  are judged by; the paper's Krum per probe is closed here into one Gram
+  matrix and one statistics pass (flr_fang_krum_rows); it needs whole rows.
+  fang_trim_: per coordinate the attackers sit just beyond the benign extreme
+  on the side opposite s, at points drawn per attacker — the worst case of
+  trimmed_mean, median, Bulyan's second stage and robust_lr round them; one
+  coordinate-wise pass (flr_fang_trim_rows) with a counter-based generator
+  keyed by the coordinate's index, so it runs on a rank's all-to-all slice.
 """
 from __future__ import annotations
 
@@ -173,6 +187,54 @@ def model_replacement_(X, f: int, global_flat: torch.Tensor, boost: Optional[flo
     1 a non-finite attacker) as device tensors."""
     M = X if isinstance(X, torch.Tensor) else X.X
     return replace_rows_(M, int(f), global_flat, *replacement_config(M.shape[0], int(f), boost, stealth, stat, rho))
+
+
+def fang_krum_config(K: int, f: int, threshold=ops.FANG_THRESHOLD) -> float:
+    """fang_krum_'s threshold checked on the host with the shape: a finite
+    number > 0, f >= 1, Krum's own K >= 2f + 3, at most 1024 benign rows."""
+    return ops._fang_krum_shape(K, f, threshold)[2]
+
+
+def fang_krum_(X, f: int, global_flat: torch.Tensor, threshold: float = ops.FANG_THRESHOLD):
+    """Fang et al.'s Krum attack, in place on a float32 device matrix or a
+    ClientMatrix: rows 0..f-1 <- g - lambda * s, g = global_flat (the model the
+    round trained from), s = sign(mu - g) with sign(0) = 0, mu the mean of rows
+    f..K-1, lambda the largest lambda0 * 2^-t above threshold for which Krum with
+    num_malicious = f picks one of those rows (lambda0 the paper's upper bound).
+    The search is closed on the device: one Gram matrix and one statistics pass
+    over the benign rows, no pass per probe, no host round trip.  Returns (lambda,
+    a float64 device scalar — NaN: a benign row held a NaN and the rows were left
+    as they were —, info int32 [2]: status 0 found, 1 threshold reached without
+    success (usual with f = 1), 2 no direction (mu == g: the rows become g), 3 not
+    finite; and t, the halvings)."""
+    M = X if isinstance(X, torch.Tensor) else X.X
+    threshold = fang_krum_config(M.shape[0], int(f), threshold)
+    return ops.fang_krum_rows(M, int(f), global_flat, threshold)
+
+
+def fang_trim_config(K: int, f: int, b=2.0) -> float:
+    """fang_trim_'s b checked on the host with the shape: finite and > 1 in
+    float32, 1 <= f < K."""
+    if not 1 <= f < K:
+        raise ValueError(f"the trimmed-mean attack needs 1 <= f < K (got f = {f}, K = {K})")
+    return ops._fang_trim_b(b)
+
+
+def fang_trim_(X, f: int, global_flat: torch.Tensor, b: float = 2.0, seed: int = 0, stream: int = 0,
+               col0: int = 0) -> None:
+    """Fang et al.'s trimmed-mean / median attack, in place on a float32 device
+    matrix or a ClientMatrix: per coordinate, rows 0..f-1 <- points just beyond
+    the benign rows' (f..K-1) extreme on the side opposite s = sign(mu - g), each
+    attacker at a draw of its own between the extreme and the extreme scaled by b
+    (the paper's b = 2) away from the benign values; a coordinate with mu == g
+    gets mu.  The draws are keyed by (seed, the coordinate's index col0 + k in
+    the order the matrix is held in, the attacker, stream): a column range called
+    with its own col0 gives the whole call's bits, stream is the round index, and
+    a matrix held in another coordinate order draws other values for the same
+    parameter."""
+    M = X if isinstance(X, torch.Tensor) else X.X
+    b = fang_trim_config(M.shape[0], int(f), b)
+    ops.fang_trim_rows(M, int(f), global_flat, b, seed, stream, col0)
 
 
 class Backdoor:

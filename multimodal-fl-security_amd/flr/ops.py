@@ -383,6 +383,119 @@ def scale_rows_from(X: torch.Tensor, center: torch.Tensor, gamma32: torch.Tensor
     return X
 
 
+FANG_THRESHOLD = 1e-5        # FLR_FANG_THRESHOLD, the paper's
+FANG_MAX_BENIGN = 1024       # flr_fang_krum_*'s limit on K - f
+
+
+def _fang_krum_shape(K: int, f: int, threshold) -> Tuple[int, int, float]:
+    """(K, f, threshold) of the Krum attack checked on the host."""
+    K, f = int(K), int(f)
+    threshold = _positive_finite(threshold, "threshold")
+    if f < 1 or K < 2 * f + 3:
+        raise ValueError(f"the Krum attack needs f >= 1 and Krum's own K >= 2f + 3 (got K = {K}, f = {f})")
+    if K - f > FANG_MAX_BENIGN:
+        raise ValueError(f"the Krum attack handles at most {FANG_MAX_BENIGN} benign rows, got {K - f}")
+    return K, f, threshold
+
+
+def fang_krum_strength(G: torch.Tensor, b: torch.Tensor, c: torch.Tensor, K: int, f: int,
+                       threshold: float = FANG_THRESHOLD):
+    """The Krum attack's strength (flr_fang_krum_strength; the arithmetic in
+    include/flr.h): the largest lambda = lambda0 * 2^-t for which Krum picks a row
+    g - lambda * s, from the benign rows' centered Gram matrix G (float64 [K - f,
+    K - f], rows_gram(X[f:], center=g)), b (float64 [K - f], b_i = <s, x_i - g>)
+    and c (float64 scalar or [1], <s, s>).  Returns (lambda64 float64 scalar,
+    lambda32 float32 scalar, info int32 [2] — status (0 found, 1 threshold
+    reached, 2 no direction, 3 not finite) and t —, stats float64 [5]: lambda0,
+    T, E, the last probe's S_att and S_min) as device tensors; no host
+    synchronisation."""
+    K, f, threshold = _fang_krum_shape(K, f, threshold)
+    nb = K - f
+    if not isinstance(G, torch.Tensor) or not G.is_cuda:
+        raise RuntimeError("G must be a CUDA/HIP tensor (the engine has no CPU path)")
+    if G.dtype != torch.float64 or tuple(G.shape) != (nb, nb) or not G.is_contiguous():
+        raise ValueError(f"G must be a contiguous float64 [{nb}, {nb}] matrix")
+    _check_vector(b, nb, G.device, "b", torch.float64)
+    _check_vector(c, 1, G.device, "c", torch.float64)
+    lam64 = torch.empty((), dtype=torch.float64, device=G.device)
+    lam32 = torch.empty((), dtype=torch.float32, device=G.device)
+    info = torch.empty(2, dtype=torch.int32, device=G.device)
+    stats = torch.empty(5, dtype=torch.float64, device=G.device)
+    nbytes = int(_capi.lib().flr_fang_krum_strength_workspace(K, f))
+    ws, wp = _ws(nbytes, G.device)
+    _capi.call("flr_fang_krum_strength", G.data_ptr(), b.data_ptr(), c.data_ptr(), K, f, threshold, lam64.data_ptr(),
+               lam32.data_ptr(), info.data_ptr(), stats.data_ptr(), wp, nbytes, _stream(G))
+    return lam64, lam32, info, stats
+
+
+def fang_krum_rows(X: torch.Tensor, nmal: int, global_flat: torch.Tensor, threshold: float = FANG_THRESHOLD,
+                   diagnostics: bool = False):
+    """Fang et al.'s Krum attack in place (flr_fang_krum_rows): rows [0, nmal) of
+    X <- g - lambda * s, g = global_flat, s = sign(mu - g) of the benign rows'
+    [nmal, K) mean, lambda the largest lambda0 * 2^-t above threshold for which
+    Krum (num_malicious = nmal) picks one of those rows, solved on the device in
+    closed form.  The whole call is enqueued on the current stream: no host
+    synchronisation.  Returns (lambda float64 device scalar — NaN: a statistic was
+    not finite and no row was written —, info int32 [2]: status, t), or with
+    diagnostics (lambda, info, stats float64 [nb + 6] — b_i, c, lambda0, T, E,
+    S_att, S_min —, G float64 [nb, nb], mu float32 [P], s float32 [P]) as device
+    tensors."""
+    K, P, ldx = _check_matrix(X)
+    K, nmal, threshold = _fang_krum_shape(K, nmal, threshold)
+    _check_vector(global_flat, P, X.device, "global_flat")
+    nb = K - nmal
+    lam = torch.empty((), dtype=torch.float64, device=X.device)
+    info = torch.empty(2, dtype=torch.int32, device=X.device)
+    stats = G = None
+    if diagnostics:
+        stats = torch.empty(nb + 6, dtype=torch.float64, device=X.device)
+        G = torch.empty((nb, nb), dtype=torch.float64, device=X.device)
+    nbytes = int(_capi.lib().flr_fang_krum_workspace(K, P, nmal))
+    ws, wp = _ws(nbytes, X.device)
+    _capi.call("flr_fang_krum_rows", X.data_ptr(), K, P, ldx, nmal, global_flat.data_ptr(), threshold, lam.data_ptr(),
+               info.data_ptr(), _ptr(stats), _ptr(G), wp, nbytes, _stream(X))
+    if not diagnostics:
+        return lam, info
+    off = wp - ws.data_ptr()
+    sgn = off + (4 * P + 255) // 256 * 256
+    return (lam, info, stats, G, ws[off:off + 4 * P].view(torch.float32).clone(),
+            ws[sgn:sgn + 4 * P].view(torch.float32).clone())
+
+
+def _fang_trim_b(b) -> float:
+    """b as the float32 value the kernel gets: a finite number > 1 (a bool or a
+    string is not one; the paper uses 2)."""
+    ok = not isinstance(b, bool) and isinstance(b, (int, float)) and abs(b) < 2.0 ** 128
+    b32 = ctypes.c_float(b).value if ok else 0.0
+    if not 1.0 < b32 < float("inf"):
+        raise ValueError(f"b must be a finite number > 1 in float32, got {b!r}")
+    return b32
+
+
+def fang_trim_rows(X: torch.Tensor, nmal: int, global_flat: torch.Tensor, b: float = 2.0, seed: int = 0,
+                   stream: int = 0, col0: int = 0) -> torch.Tensor:
+    """Fang et al.'s trimmed-mean / median attack in place (flr_fang_trim_rows):
+    per coordinate, rows [0, nmal) of X <- points drawn just beyond the benign
+    rows' [nmal, K) extreme on the side opposite s = sign(mu - g), g =
+    global_flat: between the minimum mn and mn / b (mn > 0) or mn * b where s > 0,
+    between the maximum mx and mx * b (mx > 0) or mx / b where s < 0, mu where s
+    == 0.  The draws are Philox4x32-10 keyed by seed (64 bits) with the counter
+    (col0 + column, row, stream): a column range of X called with its own col0
+    gives the whole-matrix call's bits; stream (32 bits) is the round index.
+    Returns X."""
+    K, P, ldx = _check_matrix(X)
+    nmal, seed, stream, col0 = int(nmal), int(seed), int(stream), int(col0)
+    if not 1 <= nmal < K:
+        raise ValueError(f"fang_trim_rows needs 1 <= nmal < K (got nmal = {nmal}, K = {K})")
+    _check_vector(global_flat, P, X.device, "global_flat")
+    b = _fang_trim_b(b)
+    if col0 < 0 or not 0 <= stream < 2 ** 32:
+        raise ValueError(f"fang_trim_rows needs col0 >= 0 and 0 <= stream < 2^32 (got {col0}, {stream})")
+    _capi.call("flr_fang_trim_rows", X.data_ptr(), K, P, ldx, nmal, global_flat.data_ptr(), b, seed % 2 ** 64, stream,
+               col0, _stream(X))
+    return X
+
+
 def centered_clip(X: torch.Tensor, v0: torch.Tensor, tau: float, iters: int, out: Optional[torch.Tensor] = None,
                   diagnostics: bool = False):
     """Centered clipping (flr_centered_clip): from v0, iters times

@@ -28,7 +28,8 @@ import torch
 from . import _capi
 from . import dist as fdist
 from . import ops
-from .attacks import PERTURBATIONS, Backdoor, alie_z, poison_batches_, replace_rows_, replacement_config
+from .attacks import (PERTURBATIONS, Backdoor, alie_z, fang_krum_config, fang_trim_config, poison_batches_,
+                      replace_rows_, replacement_config)
 from .defenses import get_defense
 from .defenses.krum import DeadTaps
 from .matrix import ClientMatrix
@@ -37,7 +38,8 @@ from .models.multimodal import ModelSpec, model_class, param_layout
 from .train import ClientBatchTrainer, TrainConfig, make_dropout_masks, synthetic_batches
 
 
-ATTACKS = ("sign_flip", "backdoor", "none", "alie", "ipm", "min_max", "min_sum", "model_replacement")
+ATTACKS = ("sign_flip", "backdoor", "none", "alie", "ipm", "min_max", "min_sum", "model_replacement", "fang_krum",
+           "fang_trim")
 
 
 @dataclass
@@ -49,7 +51,9 @@ class RoundConfig:
     # "sign_flip" (model_poisoning.py:274-276) | "backdoor" | "none" | "alie" | "ipm" (the colluding attacks of
     # flr.attacks: one flr_collude_rows pass between the exchange and the defense) | "min_max" | "min_sum" (one
     # flr_minmax_rows call in the same slot; whole rows: the all-gather exchange unless world == 1) |
-    # "model_replacement" (the backdoor's data, then the attackers' rows boosted about the global model in that slot)
+    # "model_replacement" (the backdoor's data, then the attackers' rows boosted about the global model in that slot) |
+    # "fang_krum" (Fang et al.'s Krum attack, one flr_fang_krum_rows call in that slot; whole rows, as min_max) |
+    # "fang_trim" (their trimmed-mean attack, one coordinate-wise flr_fang_trim_rows pass; runs on an all-to-all slice)
     attack: str = "sign_flip"
     num_attackers: int = 25              # f = int(0.2 K), clients 0..f-1 (experiment_matrix.py:67-68)
     seed: int = 42                       # run_experiments.py:43
@@ -66,7 +70,8 @@ class RoundConfig:
     # "z" (alie; default alie_z(K, f)), "epsilon" (ipm; default 0.5), "perturb" (min_max / min_sum: "std" (default) |
     # "sign" | "unit", the direction of flr.attacks.min_max_); model_replacement: "boost" (default num_clients /
     # num_attackers), "stealth" ("none" (default) | "norm" | "distance"), "stat" (norm: "median" (default) | "max" |
-    # "mean"), "rho" (default 1.0), the arguments of flr.attacks.model_replacement_
+    # "mean"), "rho" (default 1.0), the arguments of flr.attacks.model_replacement_; fang_krum: "threshold" (default
+    # 1e-5); fang_trim: "b" (default 2.0), "seed" (default the round config's seed): flr.attacks.fang_krum_ / fang_trim_
     attack_cfg: Dict = field(default_factory=dict)
 
 
@@ -129,6 +134,30 @@ class RoundEngine:
                                  "rows (row norms and distances, not a coordinate-wise statistic): use "
                                  "exchange='allgather' (a rank's all-to-all slice is the whole matrix only at "
                                  "world 1)")
+        # Fang et al.'s attacks.  fang_krum: the threshold of the one flr_fang_krum_rows call per round; attack_gamma
+        # is then lambda (a float64 device scalar) and attack_status its info, int32 [2]: status and halvings.
+        # fang_trim: (b, seed) of the one flr_fang_trim_rows pass; its draws are keyed by the coordinate's index in
+        # the order the matrix is held in (torch order here, col0 = the rank's first coordinate) and by the round
+        self._fang_krum = self._fang_trim = None
+        if rcfg.attack in ("fang_krum", "fang_trim"):
+            keys = {"threshold"} if rcfg.attack == "fang_krum" else {"b", "seed"}
+            unknown = set(rcfg.attack_cfg) - keys
+            if unknown:
+                raise ValueError(f"attack_cfg keys {sorted(unknown)} are not {rcfg.attack}'s "
+                                 f"({', '.join(sorted(keys))})")
+        if rcfg.attack == "fang_krum":
+            self._fang_krum = fang_krum_config(rcfg.num_clients, rcfg.num_attackers,
+                                               rcfg.attack_cfg.get("threshold", ops.FANG_THRESHOLD))
+            if rcfg.exchange == "alltoall" and world > 1:  # "auto" takes the all-gather exchange below
+                raise ValueError("attack 'fang_krum' needs whole client rows (row distances, not a coordinate-wise "
+                                 "statistic): use exchange='allgather' (a rank's all-to-all slice is the whole "
+                                 "matrix only at world 1)")
+        if rcfg.attack == "fang_trim":
+            seed = rcfg.attack_cfg.get("seed", rcfg.seed)
+            if isinstance(seed, bool) or not isinstance(seed, int):
+                raise ValueError(f"attack_cfg['seed'] must be an integer, got {seed!r}")
+            self._fang_trim = (fang_trim_config(rcfg.num_clients, rcfg.num_attackers, rcfg.attack_cfg.get("b", 2.0)),
+                               seed)
         defer = os.environ.get("FLR_DEFER_DEAD", "2")
         if defer == "1":  # loud: an old A/B script must not report numbers for another mode
             raise ValueError("FLR_DEFER_DEAD=1 (the dead-tap fill on a side stream beside the Krum chains) was "
@@ -162,7 +191,8 @@ class RoundEngine:
         mode = rcfg.exchange
         if mode == "auto":
             mode = "alltoall" if (self.defense.supports_sharded and PW_SLICES % world == 0
-                                  and self._minmax is None and not self._replace_whole_rows) else "allgather"
+                                  and self._minmax is None and not self._replace_whole_rows
+                                  and self._fang_krum is None) else "allgather"
         if mode not in ("alltoall", "allgather"):
             raise ValueError(f"unknown exchange mode {rcfg.exchange!r}")
         if mode == "alltoall" and not self.defense.supports_sharded:
@@ -190,9 +220,10 @@ class RoundEngine:
         # the trainer's coordinate order, written by the last optimizer step;
         # gtrain is the global model in that order (FLR_ORDER=torch: off)
         # Min-Max / Min-Sum read the round's global model beside the matrix: torch
-        # order, where global_flat lines up with the columns (model replacement likewise)
+        # order, where global_flat lines up with the columns (model replacement and Fang et al.'s attacks likewise)
         self.train_order = (getattr(self.defense, "order_free", False) and not self._wants_global
                             and self._minmax is None and self._replace is None
+                            and self._fang_krum is None and self._fang_trim is None
                             and os.environ.get("FLR_ORDER", "train") != "torch")
         bounds = None
         if self.train_order and getattr(self.defense, "needs_tap_blocks", False):
@@ -400,7 +431,7 @@ class RoundEngine:
         if self.exchange == "alltoall":
             cs = self._slice = self.xchg.exchange(self.trainer.X.data)
             # coordinate-wise: this rank's slice needs no other
-            self._apply_collusion(cs.X, self.global_flat[cs.begin:cs.end])
+            self._apply_collusion(cs.X, self.global_flat[cs.begin:cs.end], cs.begin)
             if self._wants_global:  # the robust learning rate: global_flat is overwritten below
                 kw["global_flat"] = self.global_flat[cs.begin:cs.end].clone()
             try:
@@ -419,14 +450,19 @@ class RoundEngine:
             agg = self._fallback(e, self._full.X)
         return self._publish(agg)
 
-    def _apply_collusion(self, X: torch.Tensor, g: Optional[torch.Tensor] = None) -> None:
+    def _apply_collusion(self, X: torch.Tensor, g: Optional[torch.Tensor] = None, col0: int = 0) -> None:
         """attack "alie" / "ipm" / "min_max" / "min_sum": the attackers (clients
         0..f-1, who trained honestly) replace their rows of the exchanged matrix
         by the colluding vector, computed from the benign rows — after the
         exchange, before the defense, outside the captured training graph.
         "model_replacement": they boost their own (backdoored) rows about the
         global model; g is global_flat, or its slice beside a rank's coordinate
-        range (stealth "none" alone runs there: it is coordinate-wise)."""
+        range (stealth "none" alone runs there: it is coordinate-wise).
+        "fang_krum" / "fang_trim": Fang et al.'s attacks in the same slot;
+        fang_trim is coordinate-wise and runs on a rank's range too, its draws
+        keyed by the coordinate's index in the order the matrix is held in
+        (col0 + the column: torch order, col0 the range's first coordinate),
+        the attacker and the round counter."""
         if self._collude is not None:
             ops.collude_rows(X, self.rcfg.num_attackers, *self._collude)
         if self._minmax is not None:  # global_flat: still the model this round trained from
@@ -434,6 +470,13 @@ class RoundEngine:
         if self._replace is not None:
             self.attack_gamma, self.attack_status, self.attack_flags = replace_rows_(
                 X, self.rcfg.num_attackers, self.global_flat if g is None else g, *self._replace)
+        if self._fang_krum is not None:
+            self.attack_gamma, self.attack_status = ops.fang_krum_rows(X, self.rcfg.num_attackers, self.global_flat,
+                                                                       self._fang_krum)
+        if self._fang_trim is not None:
+            b, seed = self._fang_trim
+            ops.fang_trim_rows(X, self.rcfg.num_attackers, (self.global_flat if g is None else g).contiguous(), b,
+                               seed, self.round_index % 2 ** 32, col0)
 
     def _fallback(self, err: Exception, X: torch.Tensor) -> torch.Tensor:
         """robust_server.py:120-122: a failing defense falls back to FedAvg
