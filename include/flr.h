@@ -1205,6 +1205,29 @@ int flr_gru_fwd_fused_ex(const float* gi, const float* whh, int shared_w, const 
 int flr_gru_bwd_fused_ex(const float* whhT, int shared_w, const float* gates, const float* hseq,
                          float* dgh, float* dgi, float* dh_direct, float* dh0, int64_t K,
                          int64_t B, int64_t T, int64_t H, int64_t t, void* stream);
+/* The whole recurrence in one launch per pass: one workgroup per client loops
+ * over the time steps, h_t / dgh_t handed from step to step through LDS.
+ * flr_gru_fwd_seq is flr_gru_fwd_fused_ex for t = 0 .. T-1 (reads hseq[:, 0],
+ * writes hseq[:, 1..T] and gates); flr_gru_bwd_seq is flr_gru_bwd_step at
+ * T-1 from dh = dL/dh_T, then flr_gru_bwd_fused_ex for t = T-1 .. 1 (writes
+ * all of dgh and dgi; dh_direct as the last step leaves it; dh0, optional,
+ * as the t = 1 call writes it, so only when T >= 2).  Results are the per-step
+ * default form's bit for bit.  Shapes: B <= 32, H % 32 == 0, H <= 256, any
+ * T >= 1; otherwise, and with FLR_GRU_SEQ=0 (flr_set_knob, read per call),
+ * FLR_ERR_UNSUPPORTED and nothing is written: use the per-step calls.
+ * flr_gru_seq_supported: 1 when the two would run this shape now, else 0.
+ * flr_gru_seq_preferred: 1 when a caller with both forms should take this one
+ * (supported, and K * H/32 > 768, from where it measured faster than the
+ * per-step launches on MI355X; FLR_GRU_SEQ=1: wherever supported), else 0.
+ * flr_gru_zero_h0: hseq[:, 0] = 0, the one slot the forward does not write. */
+int flr_gru_fwd_seq(const float* gi, const float* whhP, int shared_w, const float* bhh, float* hseq, float* gates,
+                    int64_t K, int64_t B, int64_t T, int64_t H, void* stream);
+int flr_gru_bwd_seq(const float* whhTP, int shared_w, const float* gates, const float* hseq, const float* dh,
+                    float* dgh, float* dgi, float* dh_direct, float* dh0, int64_t K, int64_t B, int64_t T,
+                    int64_t H, void* stream);
+int flr_gru_seq_supported(int64_t K, int64_t B, int64_t T, int64_t H);
+int flr_gru_seq_preferred(int64_t K, int64_t B, int64_t T, int64_t H);
+int flr_gru_zero_h0(float* hseq, int64_t K, int64_t B, int64_t T, int64_t H, void* stream);
 /* Pack a per-client weight into the fused kernels' MFMA-fragment order: the
  * [NG*H][C] operand (trans = 0: w is [NG*H][C]; trans = 1, NG = 1: w is [C][H]
  * and the operand is its transpose) in 32-row blocks x 16-deep k-steps, each

@@ -563,7 +563,14 @@ class Net {
     const bool fused = B_ <= 32;
     // first step in training order: one packed copy of the global W_hh for every client
     const bool wsh = first_ && gshared_ != nullptr;
-    if (fused) {
+    // the whole recurrence in one launch per pass where the shape allows and K is
+    // large enough for it to pay (FLR_GRU_SEQ=0: per step; =1: wherever eligible)
+    const bool seq = fused && flr_gru_seq_preferred(K_, B_, T_, H_) != 0;
+    if (seq) {
+      FLR_TRY(flr_gru_zero_h0(hseq_, K_, B_, T_, H_, ts));  // the launch writes every later slot
+      FLR_TRY(flr_gru_pack(wsh ? gshared_ + whh.off : whh.w, wsh ? 1 : K_, 3, H_, H_, 0, whhP_, ts));
+      FLR_TRY(flr_gru_fwd_seq(gi_, whhP_, wsh ? 1 : 0, bhh.w, hseq_, gates_, K_, B_, T_, H_, ts));
+    } else if (fused) {
       FLR_TRY(flr_fill(hseq_, K_ * (T_ + 1) * B_ * H_, 0.f, ts));
       FLR_TRY(flr_gru_pack(wsh ? gshared_ + whh.off : whh.w, wsh ? 1 : K_, 3, H_, H_, 0, whhP_, ts));
       for (int64_t t = 0; t < T_; ++t)
@@ -654,7 +661,11 @@ class Net {
     FLR_TRY(rowsum(dpre_, B_ * F_, F_, B_, F_, b1.g, st));
     if (conc) FLR_TRY(fork(st, ts, 2));
     // GRU (ClientGRU.backward)
-    if (fused) {
+    if (seq) {
+      FLR_TRY(flr_gru_pack(wsh ? gshared_ + whh.off : whh.w, wsh ? 1 : K_, 1, H_, H3, 1, whhT_, ts));
+      FLR_TRY(flr_gru_bwd_seq(whhT_, wsh ? 1 : 0, gates_, hseq_, dh_, dgh_, dgi_, dh_direct_, nullptr, K_, B_, T_, H_,
+                              ts));
+    } else if (fused) {
       FLR_TRY(flr_gru_pack(wsh ? gshared_ + whh.off : whh.w, wsh ? 1 : K_, 1, H_, H3, 1, whhT_, ts));
       FLR_TRY(flr_gru_bwd_step(dh_, gates_, hseq_, dgh_, dgi_, dh_direct_, K_, B_, T_, H_, T_ - 1, ts));
       for (int64_t t = T_ - 1; t > 0; --t)

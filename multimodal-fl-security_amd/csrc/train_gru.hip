@@ -31,6 +31,40 @@ constexpr int THREADS = 256;
 
 __device__ __forceinline__ float sigm(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// One element's gate math from gi, gh = h W_hh^T + b_hh and h_t: every forward
+// kernel calls this, so their r, z, n, h' agree bit for bit.
+struct Gate {
+  float r, z, n, h;
+};
+__device__ __forceinline__ Gate gate_math(float gir, float giz, float gin, float ghr, float ghz, float hn, float hp) {
+  Gate o;
+  o.r = sigm(gir + ghr);
+  o.z = sigm(giz + ghz);
+  o.n = tanhf(gin + o.r * hn);
+  o.h = (hp - o.n) * o.z + o.n;  // h_{t+1}
+  return o;
+}
+
+// One element's backward from dy = dL/dh_{t+1}: d(gh) = (drp, dzp, dnr),
+// d(gi) = (drp, dzp, dnp), dhd = dL/dh_t through the z-gate path.  Every
+// backward kernel calls this.
+struct ElemBwd {
+  float drp, dzp, dnp, dnr, dhd;
+};
+__device__ __forceinline__ ElemBwd elem_bwd(float dy, float r, float z, float n, float hn, float hp) {
+  const float dz = dy * (hp - n);
+  const float dn = dy * (1.0f - z);
+  const float dnp = dn * (1.0f - n * n);
+  const float dr = dnp * hn;
+  ElemBwd o;
+  o.drp = dr * (r * (1.0f - r));
+  o.dzp = dz * (z * (1.0f - z));
+  o.dnp = dnp;
+  o.dnr = dnp * r;
+  o.dhd = dy * z;
+  return o;
+}
+
 struct Dims {
   int K, B, T, H, t;
   int wshared;  // 1: every client reads the one packed W_hh copy (the first local step)
@@ -56,15 +90,13 @@ __global__ __launch_bounds__(THREADS) void fwd_step_kernel(const float* __restri
   const float* ghr = gh + kb * 3 * H;
   const int64_t hrow = (((int64_t)k * (d.T + 1) + d.t) * d.B + b) * H;
   const float hp = hseq[hrow + j];
-  const float r = sigm(gir[j] + ghr[j]);
-  const float z = sigm(gir[H + j] + ghr[H + j]);
   const float hn = ghr[2 * H + j];
-  const float n = tanhf(gir[2 * H + j] + r * hn);
-  hseq[hrow + (int64_t)d.B * H + j] = (hp - n) * z + n;  // h_{t+1}
+  const Gate o = gate_math(gir[j], gir[H + j], gir[2 * H + j], ghr[j], ghr[H + j], hn, hp);
+  hseq[hrow + (int64_t)d.B * H + j] = o.h;
   float* g = gates + (((int64_t)k * d.T + d.t) * d.B + b) * 4 * H;
-  g[j] = r;
-  g[H + j] = z;
-  g[2 * H + j] = n;
+  g[j] = o.r;
+  g[H + j] = o.z;
+  g[2 * H + j] = o.n;
   g[3 * H + j] = hn;
 }
 
@@ -85,22 +117,16 @@ __global__ __launch_bounds__(THREADS) void bwd_step_kernel(const float* __restri
   const float* g = gates + srow * 4 * H;
   const float r = g[j], z = g[H + j], n = g[2 * H + j], hn = g[3 * H + j];
   const float hp = hseq[(((int64_t)k * (d.T + 1) + d.t) * d.B + b) * H + j];
-  const float dy = dh[idx];
-  const float dz = dy * (hp - n);
-  const float dn = dy * (1.0f - z);
-  const float dnp = dn * (1.0f - n * n);
-  const float dr = dnp * hn;
-  const float drp = dr * (r * (1.0f - r));
-  const float dzp = dz * (z * (1.0f - z));
+  const ElemBwd eb = elem_bwd(dh[idx], r, z, n, hn, hp);
   float* o = dgh + srow * 3 * H;
-  o[j] = drp;
-  o[H + j] = dzp;
-  o[2 * H + j] = dnp * r;
+  o[j] = eb.drp;
+  o[H + j] = eb.dzp;
+  o[2 * H + j] = eb.dnr;
   float* q = dgi + (kb * d.T + d.t) * 3 * H;
-  q[j] = drp;
-  q[H + j] = dzp;
-  q[2 * H + j] = dnp;
-  dh_direct[idx] = dy * z;
+  q[j] = eb.drp;
+  q[H + j] = eb.dzp;
+  q[2 * H + j] = eb.dnp;
+  dh_direct[idx] = eb.dhd;
 }
 
 // ---- fused per-step kernels: the recurrence GEMM with the gate math in its
@@ -113,15 +139,21 @@ __global__ __launch_bounds__(THREADS) void bwd_step_kernel(const float* __restri
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+__device__ __forceinline__ void split1(float v, __bf16& hi, __bf16& mid, __bf16& lo) {
+  hi = (__bf16)v;
+  const float r1 = v - (float)hi;
+  mid = (__bf16)r1;
+  lo = (__bf16)(r1 - (float)mid);
+}
+
 __device__ __forceinline__ void split3(const float (&v)[8], bf16x8& hi, bf16x8& mid, bf16x8& lo) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    const __bf16 a = (__bf16)v[j];
-    const float r1 = v[j] - (float)a;
-    const __bf16 b = (__bf16)r1;
+    __bf16 a, b, c;
+    split1(v[j], a, b, c);
     hi[j] = a;
     mid[j] = b;
-    lo[j] = (__bf16)(r1 - (float)b);
+    lo[j] = c;
   }
 }
 
@@ -310,14 +342,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SEQ ? 4
     }
     const int64_t hrw = (((int64_t)k * (d.T + 1) + d.t) * B + b) * H;
     const float ghr = pbh[i][0] + v[0], ghz = pbh[i][1] + v[1], hn = pbh[i][2] + v[2];
-    const float r = sigm(pgi[i][0] + ghr);
-    const float z = sigm(pgi[i][1] + ghz);
-    const float n = tanhf(pgi[i][2] + r * hn);
-    hseq[hrw + (int64_t)B * H + j] = (php[i] - n) * z + n;  // h_{t+1}
+    const Gate o = gate_math(pgi[i][0], pgi[i][1], pgi[i][2], ghr, ghz, hn, php[i]);
+    hseq[hrw + (int64_t)B * H + j] = o.h;
     float* gg = gates + (((int64_t)k * d.T + d.t) * B + b) * 4 * H;
-    gg[j] = r;
-    gg[H + j] = z;
-    gg[2 * H + j] = n;
+    gg[j] = o.r;
+    gg[H + j] = o.z;
+    gg[2 * H + j] = o.n;
     gg[3 * H + j] = hn;
   }
 }
@@ -413,23 +443,17 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SEQ ? 6
     if (dh0) dh0[idx] = dy;
     if (!elem) continue;
     // step t-1's element backward (bwd_step_kernel's math)
-    const float r = pg[i][0], z = pg[i][1], n = pg[i][2], hn = pg[i][3];
-    const float dz = dy * (php[i] - n);
-    const float dn = dy * (1.0f - z);
-    const float dnp = dn * (1.0f - n * n);
-    const float dr = dnp * hn;
-    const float drp = dr * (r * (1.0f - r));
-    const float dzp = dz * (z * (1.0f - z));
+    const ElemBwd eb = elem_bwd(dy, pg[i][0], pg[i][1], pg[i][2], pg[i][3], php[i]);
     const int64_t srow = ((int64_t)k * d.T + d.t) * B + b;
     float* o = dgh + srow * 3 * H;
-    o[j] = drp;
-    o[H + j] = dzp;
-    o[2 * H + j] = dnp * r;
+    o[j] = eb.drp;
+    o[H + j] = eb.dzp;
+    o[2 * H + j] = eb.dnr;
     float* q = dgi + (kb * d.T + d.t) * 3 * H;
-    q[j] = drp;
-    q[H + j] = dzp;
-    q[2 * H + j] = dnp;
-    dh_direct[idx] = dy * z;
+    q[j] = eb.drp;
+    q[H + j] = eb.dzp;
+    q[2 * H + j] = eb.dnp;
+    dh_direct[idx] = eb.dhd;
   }
 }
 
@@ -461,6 +485,328 @@ __global__ __launch_bounds__(256) void pack_kernel(const float* __restrict__ w, 
     const int s = c0 / 16 + sl;
     if (s < S) dst[(int64_t)s * 512 + q * 256 + lane * 4 + e] = tile[lane & 31][sl * 16 + 8 * (lane >> 5) + 4 * q + e];
   }
+}
+
+// ---- the whole recurrence in one launch per pass.  One workgroup per client
+// loops over the time steps itself; wave ub owns the unit block ub that a
+// per-step workgroup (k, ub) owns, so no workgroup ever waits on another and
+// __syncthreads is the only synchronisation.  H % 32 == 0, H <= SEQ_HMAX; H is
+// a template parameter, so every k-step's weight offset is a constant and the
+// k-steps a range does not have are not compiled at all.
+//
+// Bit identity with the per-step default form ("8,2"): there an output
+// element's GEMM sum is SEQ_NW partials, partial w accumulated from zero over
+// wave w's k-steps [w per, min(S, (w + 1) per)) in order, then added
+// x = p0; x += p1; ...  Here the one wave computes the same partials over the
+// same ranges and adds them in the same order in registers.  (A partial is
+// never -0: its accumulator starts at +0, so the per-step form's MFMAs on the
+// zero operands of an idle k-step change nothing and are not issued here.)
+//
+// The A operand (h_t forward, dgh_t backward) is split once per step into its
+// three bf16 term images in LDS, rows padded by 16 bytes (a row of 2 H bytes
+// would put all 32 rows on the same banks); rows >= B stay zero, the zeros the
+// per-step loads return.  The packed-weight loads of range w + 1 — and across
+// the step boundary those of range 0, which do not depend on h — are issued
+// before range w's MFMAs.
+constexpr int SEQ_NW = 8;
+constexpr int SEQ_HMAX = 256;
+
+// tile row of accumulator register e for lane half h (mfma_f32_32x32x16's C map)
+__device__ __forceinline__ int tile_row(int e, int h) { return (e & 3) + 8 * (e >> 2) + 4 * h; }
+
+// GEMM geometry of a pass: NG row groups of NUB 32-row blocks, S k-steps
+template <int NG_, int NUB_, int S_>
+struct SeqGeo {
+  static constexpr int NG = NG_, NUB = NUB_, S = S_;
+  static constexpr int PER = (S + SEQ_NW - 1) / SEQ_NW;  // the per-step form's k-steps per wave
+  static constexpr int RS = 16 * S + 8;                  // image row stride (bf16)
+  static constexpr int IMG = 96 * RS;                    // three 32-row term images
+};
+template <class G>
+using WBuf = float[G::PER][G::NG][8];
+
+// The packed B fragments of range W: rw is based at this wave's block of group
+// 0, voff = lane * 16; the (group, k-step) offset rides in the scalar offset.
+template <class G, int W>
+__device__ __forceinline__ void wload(rsrc_t rw, unsigned voff, WBuf<G>& v) {
+#pragma unroll
+  for (int q = 0; q < G::PER; ++q) {
+    const int s = W * G::PER + q;
+    if (s < G::S) {
+#pragma unroll
+      for (int g = 0; g < G::NG; ++g) {
+        const int soff = ((g * G::NUB * G::S + s) * 512) * 4;
+        const f32x4 x = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, voff, soff, 0));
+        const f32x4 y = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rw, voff, soff + 1024, 0));
+        v[q][g][0] = x[0]; v[q][g][1] = x[1]; v[q][g][2] = x[2]; v[q][g][3] = x[3];
+        v[q][g][4] = y[0]; v[q][g][5] = y[1]; v[q][g][6] = y[2]; v[q][g][7] = y[3];
+      }
+    }
+  }
+}
+
+// partial W from zero over its k-steps, A fragments from the term images
+// (a: this lane's row and k half of the first image), then x = p or x += p
+template <class G, int W>
+__device__ __forceinline__ void wmma(const __bf16* a, const WBuf<G>& v, f32x16 (&x)[G::NG]) {
+  f32x16 p[G::NG];
+#pragma unroll
+  for (int g = 0; g < G::NG; ++g)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) p[g][e] = 0.f;
+#pragma unroll
+  for (int q = 0; q < G::PER; ++q) {
+    const int s = W * G::PER + q;
+    if (s < G::S) {
+      const bf16x8 ah = *reinterpret_cast<const bf16x8*>(a + 16 * s);
+      const bf16x8 am = *reinterpret_cast<const bf16x8*>(a + 16 * s + 32 * G::RS);
+      const bf16x8 al = *reinterpret_cast<const bf16x8*>(a + 16 * s + 64 * G::RS);
+#pragma unroll
+      for (int g = 0; g < G::NG; ++g) {
+        bf16x8 bh, bm, bl;
+        split3(v[q][g], bh, bm, bl);
+        p[g] = mfma6(ah, am, al, bh, bm, bl, p[g]);
+      }
+      __builtin_amdgcn_sched_barrier(0);  // one k-step's fragments live at a time: the register budget is 256
+    }
+  }
+#pragma unroll
+  for (int g = 0; g < G::NG; ++g)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) x[g][e] = W == 0 ? p[g][e] : x[g][e] + p[g][e];
+  // the sum is formed here: left free, the compiler keeps all SEQ_NW partials
+  // alive and sinks these adds into the epilogue's per-row branches
+#pragma unroll
+  for (int g = 0; g < G::NG; ++g) asm volatile("" : "+v"(x[g]));
+}
+
+// One fp32 value into the three term images: p is the lane's part of the
+// address (its 4 h rows and its column), off the element's constant part.
+template <class G>
+__device__ __forceinline__ void img_put(__bf16* p, int off, float v) {
+  __bf16 a, b, c;
+  split1(v, a, b, c);
+  p[off] = a;
+  p[off + 32 * G::RS] = b;
+  p[off + 64 * G::RS] = c;
+}
+
+// The SEQ_NW ranges of one GEMM, two register buffers alternating: range W + 1
+// loads under range W's MFMAs; `last` (the epilogue's operand loads) is issued
+// under the last range's.  On entry bA holds range 0; on exit it is free.
+template <class G, int W = 0, class Last>
+__device__ __forceinline__ void wgemm(const __bf16* a, rsrc_t rw, unsigned voff, WBuf<G>& bA, WBuf<G>& bB,
+                                      f32x16 (&x)[G::NG], Last last) {
+  wload<G, W + 1>(rw, voff, bB);
+  __builtin_amdgcn_sched_barrier(0);
+  wmma<G, W>(a, bA, x);
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (W + 2 < SEQ_NW)
+    wload<G, W + 2>(rw, voff, bA);
+  else
+    last();
+  __builtin_amdgcn_sched_barrier(0);
+  wmma<G, W + 1>(a, bB, x);
+  __builtin_amdgcn_sched_barrier(0);
+  if constexpr (W + 2 < SEQ_NW) wgemm<G, W + 2>(a, rw, voff, bA, bB, x, last);
+}
+
+// Epilogue element e of a lane is tile row tile_row(e, 0) + 4 h: its address in
+// any of the arrays is one per-lane byte offset (the 4 h rows and the column)
+// plus a wave-uniform one (the row's e part, the time step), which rides in the
+// scalar offset, so an array costs one address register, not one per element.
+__device__ __forceinline__ float ldg(rsrc_t r, unsigned voff, int soff) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
+}
+__device__ __forceinline__ void stg(rsrc_t r, float v, unsigned voff, int soff) {
+  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, voff, soff, 0);
+}
+// keeps the per-element offsets derived from v out of the registers across the time loop
+__device__ __forceinline__ unsigned per_step(unsigned v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+template <int H>
+__global__ __launch_bounds__(2 * H) void fwd_seq_kernel(const float* __restrict__ gi, const float* __restrict__ whhP,
+                                                        const float* __restrict__ bhh, float* __restrict__ hseq,
+                                                        float* __restrict__ gates, const Dims d) {
+  using G = SeqGeo<3, H / 32, H / 16>;
+  __shared__ __attribute__((aligned(16))) __bf16 img[2 * G::IMG];  // two h images: one barrier per step
+  const int k = blockIdx.x, ub = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int l32 = lane & 31, h = lane >> 5, j = ub * 32 + l32;
+  const int B = d.B, T = d.T;
+  for (int i = threadIdx.x * 8; i < 2 * G::IMG; i += 2 * H * 8)
+    *reinterpret_cast<f32x4*>(img + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+  __syncthreads();
+  constexpr int64_t WN = (int64_t)3 * G::NUB * G::S * 512;  // a client's packed floats
+  const rsrc_t rw = make_rsrc(whhP + (d.wshared ? 0 : k * WN) + ub * G::S * 512, WN - ub * G::S * 512);
+  const rsrc_t rg = make_rsrc(gi + (int64_t)k * B * T * 3 * H, (int64_t)B * T * 3 * H);
+  const rsrc_t rbias = make_rsrc(bhh + (int64_t)k * 3 * H, (int64_t)3 * H);
+  const rsrc_t rh = make_rsrc(hseq + (int64_t)k * (T + 1) * B * H, (int64_t)(T + 1) * B * H);
+  const rsrc_t rgt = make_rsrc(gates + (int64_t)k * T * B * 4 * H, (int64_t)T * B * 4 * H);
+  const unsigned voff = lane * 16;
+  const unsigned vgi = (4 * h * T * 3 * H + j) * 4, vh = (4 * h * H + j) * 4, vgt = (4 * h * 4 * H + j) * 4;
+  WBuf<G> bA, bB;
+  wload<G, 0>(rw, voff, bA);
+  float hp[16], pbh[3];  // this lane's h_t (the value it stored as h_{t+1} a step earlier) and bias
+#pragma unroll
+  for (int g = 0; g < 3; ++g) pbh[g] = bload1(rbias, true, g * H + j);
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int b = tile_row(e, h);
+    hp[e] = ldg(rh, b < B ? vh : SENT, tile_row(e, 0) * H * 4);
+    if (b < B) img_put<G>(img + 4 * h * G::RS + j, tile_row(e, 0) * G::RS, hp[e]);
+  }
+  __syncthreads();
+  for (int t = 0; t < T; ++t) {
+    const __bf16* cur = img + (t & 1) * G::IMG + l32 * G::RS + 8 * h;
+    __bf16* nxt = img + ((t + 1) & 1) * G::IMG + 4 * h * G::RS + j;
+    f32x16 x[3];
+    float pgi[16][3];
+    wgemm<G>(cur, rw, voff, bA, bB, x, [&]() {
+      const unsigned v = per_step(vgi);
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const unsigned off = tile_row(e, h) < B ? v : SENT;
+#pragma unroll
+        for (int g = 0; g < 3; ++g) pgi[e][g] = ldg(rg, off + g * H * 4, ((tile_row(e, 0) * T + t) * 3 * H) * 4);
+      }
+    });
+    wload<G, 0>(rw, voff, bA);  // the next step's first range under the gate math (unused after the last step)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int b = tile_row(e, h);
+      if (b < B) {
+        const float ghr = pbh[0] + x[0][e], ghz = pbh[1] + x[1][e], hn = pbh[2] + x[2][e];
+        const Gate o = gate_math(pgi[e][0], pgi[e][1], pgi[e][2], ghr, ghz, hn, hp[e]);
+        stg(rh, o.h, vh, (((t + 1) * B + tile_row(e, 0)) * H) * 4);
+        const int sg = ((t * B + tile_row(e, 0)) * 4 * H) * 4;
+        stg(rgt, o.r, vgt, sg);
+        stg(rgt, o.z, vgt + H * 4, sg);
+        stg(rgt, o.n, vgt + 2 * H * 4, sg);
+        stg(rgt, hn, vgt + 3 * H * 4, sg);
+        hp[e] = o.h;
+        img_put<G>(nxt, tile_row(e, 0) * G::RS, o.h);
+      }
+      __builtin_amdgcn_sched_barrier(0);  // one element's exp / tanh temporaries at a time
+    }
+    __syncthreads();  // h_{t+1}'s image complete; every wave is done reading h_t's (rewritten a step later)
+  }
+}
+
+// dh: dL/dh_T [K][B][H].  Phase 1 is bwd_step_kernel at T-1; then the fused
+// steps t = T-1 .. 1.  dgh_t reaches the next GEMM through its term images in
+// LDS (one buffer of 3 x 32 x (3H + 8) bf16: 146 KB at H = 256, so two barriers
+// per step) and is stored to HBM for the dW_hh GEMM as the per-step path does.
+// dh_direct stays in registers between steps; the last step's is stored.
+template <int H>
+__global__ __launch_bounds__(2 * H) void bwd_seq_kernel(const float* __restrict__ whhTP,
+                                                        const float* __restrict__ gates,
+                                                        const float* __restrict__ hseq, const float* __restrict__ dh,
+                                                        float* __restrict__ dgh, float* __restrict__ dgi,
+                                                        float* __restrict__ dh_direct, float* __restrict__ dh0,
+                                                        const Dims d) {
+  using G = SeqGeo<1, H / 32, 3 * H / 16>;
+  constexpr int R = 3 * H;
+  __shared__ __attribute__((aligned(16))) __bf16 img[G::IMG];
+  const int k = blockIdx.x, ub = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int l32 = lane & 31, h = lane >> 5, j = ub * 32 + l32;
+  const int B = d.B, T = d.T;
+  for (int i = threadIdx.x * 8; i < G::IMG; i += 2 * H * 8)
+    *reinterpret_cast<f32x4*>(img + i) = f32x4{0.f, 0.f, 0.f, 0.f};
+  __syncthreads();
+  constexpr int64_t WN = (int64_t)G::NUB * G::S * 512;
+  const rsrc_t rw = make_rsrc(whhTP + (d.wshared ? 0 : k * WN) + ub * G::S * 512, WN - ub * G::S * 512);
+  const rsrc_t rgt = make_rsrc(gates + (int64_t)k * T * B * 4 * H, (int64_t)T * B * 4 * H);
+  const rsrc_t rhp = make_rsrc(hseq + (int64_t)k * (T + 1) * B * H, (int64_t)(T + 1) * B * H);
+  const rsrc_t rdgh = make_rsrc(dgh + (int64_t)k * T * B * R, (int64_t)T * B * R);
+  const rsrc_t rdgi = make_rsrc(dgi + (int64_t)k * B * T * R, (int64_t)B * T * R);
+  const rsrc_t rdd = make_rsrc(dh_direct + (int64_t)k * B * H, (int64_t)B * H);
+  const rsrc_t rdh0 = make_rsrc(dh0 ? dh0 + (int64_t)k * B * H : nullptr, dh0 ? (int64_t)B * H : 0);
+  const unsigned vh = (4 * h * H + j) * 4, vgt = (4 * h * 4 * H + j) * 4, vgh = (4 * h * R + j) * 4;
+  const unsigned vgi = (4 * h * T * R + j) * 4;
+  float pg[16][4], php[16];  // the gates and h_t of the element step about to run
+  auto load_epi = [&](int t) {
+    const unsigned v4 = per_step(vgt), v1 = per_step(vh);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const bool ok = tile_row(e, h) < B;
+      const int rowt = t * B + tile_row(e, 0);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) pg[e][q] = ldg(rgt, (ok ? v4 : SENT) + q * H * 4, rowt * 4 * H * 4);
+      php[e] = ldg(rhp, ok ? v1 : SENT, rowt * H * 4);
+    }
+  };
+  float dd[16];  // dh_direct of this lane's elements
+  // the element backward of step t from dy, its stores, and dgh_t's image (rows b < B only)
+  auto elem = [&](int t, int e, float dy) {
+    const ElemBwd eb = elem_bwd(dy, pg[e][0], pg[e][1], pg[e][2], pg[e][3], php[e]);
+    const int so = ((t * B + tile_row(e, 0)) * R) * 4, si = ((tile_row(e, 0) * T + t) * R) * 4;
+    stg(rdgh, eb.drp, vgh, so);
+    stg(rdgh, eb.dzp, vgh + H * 4, so);
+    stg(rdgh, eb.dnr, vgh + 2 * H * 4, so);
+    stg(rdgi, eb.drp, vgi, si);
+    stg(rdgi, eb.dzp, vgi + H * 4, si);
+    stg(rdgi, eb.dnp, vgi + 2 * H * 4, si);
+    dd[e] = eb.dhd;
+    if (t == 0) {
+      stg(rdd, eb.dhd, vh, tile_row(e, 0) * H * 4);
+    } else {
+      __bf16* p = img + 4 * h * G::RS + j;
+      img_put<G>(p, tile_row(e, 0) * G::RS, eb.drp);
+      img_put<G>(p, tile_row(e, 0) * G::RS + H, eb.dzp);
+      img_put<G>(p, tile_row(e, 0) * G::RS + 2 * H, eb.dnr);
+    }
+  };
+  load_epi(T - 1);
+  {
+    const rsrc_t rdh = make_rsrc(dh + (int64_t)k * B * H, (int64_t)B * H);
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const bool ok = tile_row(e, h) < B;
+      const float dy = ldg(rdh, ok ? vh : SENT, tile_row(e, 0) * H * 4);
+      if (ok) elem(T - 1, e, dy);
+    }
+  }
+  if (T < 2) return;  // no GEMM step: the packed weights are not read
+  const unsigned voff = lane * 16;
+  const __bf16* a = img + l32 * G::RS + 8 * h;
+  WBuf<G> bA, bB;
+  wload<G, 0>(rw, voff, bA);
+  __syncthreads();
+  for (int t = T - 1; t >= 1; --t) {
+    f32x16 x[1];
+    wgemm<G>(a, rw, voff, bA, bB, x, [&]() { load_epi(t - 1); });
+    wload<G, 0>(rw, voff, bA);  // the next step's first range under the element math (unused after the last)
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();  // every wave is done reading dgh_t's image
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      if (tile_row(e, h) < B) {
+        const float dy = dd[e] + x[0][e];  // dL/dh_t
+        if (dh0 && t == 1) stg(rdh0, dy, vh, tile_row(e, 0) * H * 4);
+        elem(t - 1, e, dy);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();
+  }
+}
+
+// hseq[:, 0] = 0: the one slot of hseq the one-launch forward reads and does not write
+__global__ __launch_bounds__(THREADS) void zero_h0_kernel(float* __restrict__ hseq, int64_t n, int64_t stride) {
+  const int64_t i = (int64_t)blockIdx.x * THREADS + threadIdx.x;
+  if (i < n) hseq[(int64_t)blockIdx.y * stride + i] = 0.f;
+}
+
+// FLR_GRU_SEQ=0 (read per call) turns the one-launch form off
+inline bool seq_shape_ok(int64_t K, int64_t B, int64_t T, int64_t H) {
+  const char* e = flr::knob("FLR_GRU_SEQ");
+  if (e && e[0] == '0') return false;
+  // byte offsets within a client's arrays (32 tile rows, 4 H the widest row) stay below 2 GB
+  return B <= 32 && H % 32 == 0 && H <= SEQ_HMAX && 32 * (T + 1) * 4 * H < (int64_t)1 << 29;
 }
 
 inline bool dims_ok(int64_t K, int64_t B, int64_t T, int64_t H, int64_t t) {
@@ -571,6 +917,61 @@ extern "C" int flr_gru_bwd_fused_ex(const float* whhT, int shared_w, const float
     gru::launch_bwd<false>(cfg, dim3((unsigned)(K * nub)), as_stream(stream), whhT, gates, hseq, dgh, dgi, dh_direct,
                            dh0, d, nub);
   return launch_status("gru bwd fused");
+}
+
+extern "C" int flr_gru_seq_supported(int64_t K, int64_t B, int64_t T, int64_t H) {
+  return K > 0 && K <= 65535 && B > 0 && T > 0 && H > 0 && gru::seq_shape_ok(K, B, T, H) ? 1 : 0;
+}
+
+// A time step of the one-launch form costs about the same at every K up to
+// the CU count (one workgroup per client: 20-26 us at H = 256), a per-step
+// launch about 7 us per serial round of its K * H/32 one-per-CU workgroups
+// (tools/gru_bench.py --seq; profiles/gru_seq): the one launch pays from the
+// fourth round on.  FLR_GRU_SEQ=1 takes it at every eligible shape.
+extern "C" int flr_gru_seq_preferred(int64_t K, int64_t B, int64_t T, int64_t H) {
+  if (!flr_gru_seq_supported(K, B, T, H)) return 0;
+  const char* e = flr::knob("FLR_GRU_SEQ");
+  return (e && e[0] == '1') || K * (H / 32) > 3 * 256 ? 1 : 0;
+}
+
+extern "C" int flr_gru_zero_h0(float* hseq, int64_t K, int64_t B, int64_t T, int64_t H, void* stream) {
+  if (!hseq || K < 1 || K > 65535 || B < 1 || T < 1 || H < 1 || B * H >= (int64_t)1 << 31) return FLR_ERR_ARG;
+  const int64_t n = B * H;
+  hipLaunchKernelGGL(gru::zero_h0_kernel, dim3((unsigned)((n + gru::THREADS - 1) / gru::THREADS), (unsigned)K),
+                     dim3(gru::THREADS), 0, as_stream(stream), hseq, n, (T + 1) * n);
+  return launch_status("gru zero h0");
+}
+
+extern "C" int flr_gru_fwd_seq(const float* gi, const float* whhP, int shared_w, const float* bhh, float* hseq,
+                               float* gates, int64_t K, int64_t B, int64_t T, int64_t H, void* stream) {
+  if (!gi || !whhP || !bhh || !hseq || !gates || !gru::dims_ok(K, B, T, H, 0) || K > 65535) return FLR_ERR_ARG;
+  if (!gru::seq_shape_ok(K, B, T, H)) return FLR_ERR_UNSUPPORTED;
+  const gru::Dims d{(int)K, (int)B, (int)T, (int)H, 0, shared_w ? 1 : 0};
+  switch (H / 32) {
+#define FLR_SEQ_CASE(N) \
+  case N: hipLaunchKernelGGL(gru::fwd_seq_kernel<32 * N>, dim3((unsigned)K), dim3(64 * N), 0, as_stream(stream), gi, whhP, bhh, hseq, gates, d); break;
+    FLR_SEQ_CASE(1) FLR_SEQ_CASE(2) FLR_SEQ_CASE(3) FLR_SEQ_CASE(4) FLR_SEQ_CASE(5) FLR_SEQ_CASE(6) FLR_SEQ_CASE(7)
+    FLR_SEQ_CASE(8)
+#undef FLR_SEQ_CASE
+  }
+  return launch_status("gru fwd seq");
+}
+
+extern "C" int flr_gru_bwd_seq(const float* whhTP, int shared_w, const float* gates, const float* hseq,
+                               const float* dh, float* dgh, float* dgi, float* dh_direct, float* dh0, int64_t K,
+                               int64_t B, int64_t T, int64_t H, void* stream) {
+  if (!whhTP || !gates || !hseq || !dh || !dgh || !dgi || !dh_direct || !gru::dims_ok(K, B, T, H, 0) || K > 65535)
+    return FLR_ERR_ARG;
+  if (!gru::seq_shape_ok(K, B, T, H)) return FLR_ERR_UNSUPPORTED;
+  const gru::Dims d{(int)K, (int)B, (int)T, (int)H, 0, shared_w ? 1 : 0};
+  switch (H / 32) {
+#define FLR_SEQ_CASE(N) \
+  case N: hipLaunchKernelGGL(gru::bwd_seq_kernel<32 * N>, dim3((unsigned)K), dim3(64 * N), 0, as_stream(stream), whhTP, gates, hseq, dh, dgh, dgi, dh_direct, dh0, d); break;
+    FLR_SEQ_CASE(1) FLR_SEQ_CASE(2) FLR_SEQ_CASE(3) FLR_SEQ_CASE(4) FLR_SEQ_CASE(5) FLR_SEQ_CASE(6) FLR_SEQ_CASE(7)
+    FLR_SEQ_CASE(8)
+#undef FLR_SEQ_CASE
+  }
+  return launch_status("gru bwd seq");
 }
 
 extern "C" int flr_gru_pack(const float* w, int64_t K, int64_t NG, int64_t H, int64_t C, int trans, float* wp,

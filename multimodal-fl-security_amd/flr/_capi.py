@@ -227,7 +227,12 @@ SIGNATURES = {
     "flr_gru_pack": (_int, [_c_void_p, _i64, _i64, _i64, _i64, _int, _c_void_p, _c_void_p]),
     "flr_gru_fwd_fused_ex": (_int, [_c_void_p, _c_void_p, _int] + [_c_void_p] * 3 + [_i64] * 5 + [_c_void_p]),
     "flr_gru_bwd_fused_ex": (_int, [_c_void_p, _int] + [_c_void_p] * 6 + [_i64] * 5 + [_c_void_p]),
-    "flr_batchnorm_infer": (_int, [_c_void_p] * 7 + [_i64, _i64, ctypes.c_float, _int, _c_void_p]),
+    "flr_gru_fwd_seq": (_int, [_c_void_p, _c_void_p, _int] + [_c_void_p] * 3 + [_i64] * 4 + [_c_void_p]),
+    "flr_gru_bwd_seq": (_int, [_c_void_p, _int] + [_c_void_p] * 7 + [_i64] * 4 + [_c_void_p]),
+    "flr_gru_seq_supported": (_int, [_i64] * 4),
+    "flr_gru_seq_preferred": (_int, [_i64] * 4),
+    "flr_gru_zero_h0": (_int, [_c_void_p] + [_i64] * 4 + [_c_void_p]),
+    "flr_batchnorm_infer":(_int, [_c_void_p] * 7 + [_i64, _i64, ctypes.c_float, _int, _c_void_p]),
     "flr_classify_rows": (_int, [_c_void_p, _c_void_p, _i64, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p,
                                  _c_void_p]),
 }
