@@ -15,8 +15,8 @@
 // One stream and one event set per device, shared by every trainer of the
 // process: with FLR_SGD_OVERLAP=1 at most one training call may be in flight
 // per device at a time (two concurrent callers would record and wait on the
-// same events).  A model with more parameter groups than NEV - 1 updates on
-// the caller's stream (no overlap, same results).
+// same events).  A model with more parameter groups than the stream has events,
+// less one, updates on the caller's stream (no overlap, same results).
 //
 // Off by default (FLR_SGD_OVERLAP=1 turns it on).  Measured at C3 on MI355X
 // (tools/gpu_r3_k.sh, gpu_r3_l.sh): 79 % of the optimizer's kernel time does
@@ -33,126 +33,107 @@
 
 namespace flr {
 
-struct SideStream {
-  static constexpr int NEV = 48;
-  hipStream_t s = nullptr;
-  hipEvent_t ev[NEV] = {};
-};
-
-// The optimizer update on a side stream under the next step's forward
-// (FLR_SGD_OVERLAP=1) measured no faster: tools build only.
-inline bool side_overlap_enabled() {
-#ifdef FLR_ABLATION
-  const char* e = flr::knob("FLR_SGD_OVERLAP");
-  return e && e[0] == '1';
-#else
-  return false;
-#endif
-}
-
-// The current device's side stream; created on first use when create is set
-// (never during a capture of `st`).  nullptr: none (or overlap disabled).
-inline SideStream* side_stream(bool create, hipStream_t st = nullptr) {
-  if (!side_overlap_enabled()) return nullptr;
-  static SideStream pool[64];
-  static bool made[64] = {};
-  static std::mutex mu;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  std::lock_guard<std::mutex> lock(mu);
-  if (made[dev]) return &pool[dev];
-  if (!create) return nullptr;
-  if (st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return nullptr;
-  }
-  SideStream& ss = pool[dev];
-  if (hipStreamCreateWithFlags(&ss.s, hipStreamNonBlocking) != hipSuccess) return nullptr;
-  for (int i = 0; i < SideStream::NEV; ++i)
-    if (hipEventCreateWithFlags(&ss.ev[i], hipEventDisableTiming) != hipSuccess) return nullptr;
-  made[dev] = true;
-  return &ss;
-}
-
-// The text-branch stream of the ResNet + GRU trainer (train_clients.hip): the
-// embedding + GRU forward and backward run on it beside the image trunk (the
-// recurrence is a chain of small latency-bound launches that leaves most of the
-// chip idle), forked from and joined to the caller's stream by events (graph-
-// capturable).  One per device, created outside any capture; one training
-// call per device at a time.  FLR_TEXT_STREAM=0: everything on the caller's
-// stream (A/B, read per call).
-struct TextStream {
-  // forward fork / join, backward fork / join; 4 .. NEV - 2: the trunk's last
-  // weight gradients forked onto it (idle by then), NEV - 1 their join
-  static constexpr int NEV = 8;
-  hipStream_t s = nullptr;
-  hipEvent_t ev[NEV] = {};
-};
-
-inline bool text_stream_enabled() {
-  const char* e = flr::knob("FLR_TEXT_STREAM");
-  return !(e && e[0] == '0');
-}
-
-inline TextStream* text_stream(bool create, hipStream_t st = nullptr) {
-  if (!text_stream_enabled()) return nullptr;
-  static TextStream pool[64];
-  static bool made[64] = {};
-  static std::mutex mu;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
-  std::lock_guard<std::mutex> lock(mu);
-  if (made[dev]) return &pool[dev];
-  if (!create) return nullptr;
-  if (st) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return nullptr;
-  }
-  TextStream& ts = pool[dev];
-  if (hipStreamCreateWithFlags(&ts.s, hipStreamNonBlocking) != hipSuccess) return nullptr;
-  for (int i = 0; i < TextStream::NEV; ++i)
-    if (hipEventCreateWithFlags(&ts.ev[i], hipEventDisableTiming) != hipSuccess) return nullptr;
-  made[dev] = true;
-  return &ts;
-}
-
-// The weight-gradient stream of the native trainers: every tap-major conv's
-// weight gradient (ResNet + GRU) and every ViT layer's weight / bias gradients
+// The native trainers' three auxiliary streams.  Each is one stream and its
+// events per device, shared by every trainer of the process (one training call
+// per device at a time), created outside any capture and joined back into the
+// caller's stream within the call that forks to it.
+//
+// AUX_OPT: the optimizer's side stream described above.  FLR_SGD_OVERLAP=1
+// turns it on, and only in the tools build (FLR_ABLATION): it measured no
+// faster.
+//
+// AUX_TEXT: the text-branch stream of the ResNet + GRU trainer
+// (train_clients.hip).  The embedding + GRU forward and backward run on it
+// beside the image trunk (the recurrence is a chain of small latency-bound
+// launches that leaves most of the chip idle); the trunk's last weight
+// gradients follow on it, idle by then.  FLR_TEXT_STREAM=0: everything on the
+// caller's stream (A/B).
+//
+// AUX_WGRAD: the weight-gradient stream.  Every tap-major conv's weight
+// gradient (ResNet + GRU) and every ViT layer's weight / bias gradients
 // (ViT + BERT) run on it, forked after the layer's output gradient is ready,
 // while the caller's stream continues down the data-gradient chain (the
-// backward's critical path); joined before the clip + SGD step.  Per device,
-// created outside any capture; FLR_WGRAD_STREAM=0: off (A/B).
-struct WgradStream {
-  static constexpr int NEV = 128;
+// backward's critical path); joined before the clip + SGD step.  The ResNet's
+// forward runs its shortcut convs there.  FLR_WGRAD_STREAM=0: off (A/B).
+//
+// The gates are read per call.  The event counts decide when a trainer falls
+// back to the caller's stream (more parameter groups, layers or forks than
+// events: same results, no overlap).
+enum AuxKind { AUX_OPT = 0, AUX_TEXT = 1, AUX_WGRAD = 2, AUX_KINDS = 3 };
+constexpr int kAuxEvents[AUX_KINDS] = {48, 8, 128};
+constexpr int kAuxMaxEvents = 128;
+
+struct AuxStream {
   hipStream_t s = nullptr;
-  hipEvent_t ev[NEV] = {};
+  int nev = 0;  // events created; a stream is handed out only with its kind's full count
+  hipEvent_t ev[kAuxMaxEvents] = {};
 };
 
-inline bool wgrad_stream_enabled() {
-  const char* e = flr::knob("FLR_WGRAD_STREAM");
+inline bool aux_enabled(AuxKind kind) {
+  if (kind == AUX_OPT) {
+#ifdef FLR_ABLATION
+    const char* e = flr::knob("FLR_SGD_OVERLAP");
+    return e && e[0] == '1';
+#else
+    return false;
+#endif
+  }
+  const char* e = flr::knob(kind == AUX_TEXT ? "FLR_TEXT_STREAM" : "FLR_WGRAD_STREAM");
   return !(e && e[0] == '0');
 }
 
-inline WgradStream* wgrad_stream(bool create, hipStream_t st = nullptr) {
-  if (!wgrad_stream_enabled()) return nullptr;
-  static WgradStream pool[64];
-  static bool made[64] = {};
+// The current device's stream of one kind; created on first use when create is
+// set (never during a capture of `st`).  nullptr: none, or the kind is off.
+// A creation that fails part-way keeps what it made in the pool, and the next
+// creating call completes that set: nothing is leaked or made twice.
+inline AuxStream* aux_stream(AuxKind kind, bool create, hipStream_t st = nullptr) {
+  if (!aux_enabled(kind)) return nullptr;
+  static AuxStream pool[AUX_KINDS][64];
   static std::mutex mu;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
   std::lock_guard<std::mutex> lock(mu);
-  if (made[dev]) return &pool[dev];
+  AuxStream& a = pool[kind][dev];
+  if (a.s && a.nev == kAuxEvents[kind]) return &a;
   if (!create) return nullptr;
   if (st) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return nullptr;
   }
-  WgradStream& ws = pool[dev];
-  if (hipStreamCreateWithFlags(&ws.s, hipStreamNonBlocking) != hipSuccess) return nullptr;
-  for (int i = 0; i < WgradStream::NEV; ++i)
-    if (hipEventCreateWithFlags(&ws.ev[i], hipEventDisableTiming) != hipSuccess) return nullptr;
-  made[dev] = true;
-  return &ws;
+  if (!a.s && hipStreamCreateWithFlags(&a.s, hipStreamNonBlocking) != hipSuccess) {
+    a.s = nullptr;
+    return nullptr;
+  }
+  for (; a.nev < kAuxEvents[kind]; ++a.nev)
+    if (hipEventCreateWithFlags(&a.ev[a.nev], hipEventDisableTiming) != hipSuccess) return nullptr;
+  return &a;
 }
+
+inline AuxStream* side_stream(bool create, hipStream_t st = nullptr) { return aux_stream(AUX_OPT, create, st); }
+inline AuxStream* text_stream(bool create, hipStream_t st = nullptr) { return aux_stream(AUX_TEXT, create, st); }
+inline AuxStream* wgrad_stream(bool create, hipStream_t st = nullptr) { return aux_stream(AUX_WGRAD, create, st); }
+
+// Event links between streams (what a capture turns into the graph's edges).
+// Each returns an FLR_* status, the failure reported under the call site's label.
+inline int ev_record(hipEvent_t e, hipStream_t on, const char* where) {
+  return hipEventRecord(e, on) == hipSuccess ? FLR_OK : launch_status(where);
+}
+inline int ev_wait(hipStream_t s, hipEvent_t e, const char* where) {
+  return hipStreamWaitEvent(s, e, 0) == hipSuccess ? FLR_OK : launch_status(where);
+}
+// e recorded on `from`, then `to` waits on it: a fork, or a join made on the spot
+inline int ev_link(hipEvent_t e, hipStream_t from, hipStream_t to, const char* where) {
+  if (hipEventRecord(e, from) != hipSuccess || hipStreamWaitEvent(to, e, 0) != hipSuccess) return launch_status(where);
+  return FLR_OK;
+}
+
+// The next free event of a stream within one step or pass.  left(n): n more can
+// be taken (false without a stream).
+struct EventCursor {
+  AuxStream* a = nullptr;
+  int next = 0;
+  bool left(int n) const { return a && next + n <= a->nev; }
+  hipEvent_t take() { return a->ev[next++]; }
+};
 
 }  // namespace flr

@@ -146,6 +146,9 @@ struct Block {
   int64_t in_elems, out_elems;
 };
 
+#define FLR_TRY(x) \
+  if ((rc = (x)) != FLR_OK) return rc
+
 class Net {
  public:
   Net(const flr_resnet_gru_spec& s, int64_t K, int64_t B, float wd, float clip, char* base)
@@ -413,7 +416,7 @@ class Net {
   // read (the dead-tap slabs stay out of the training state).
   int load_global_train(const float* gtrain, hipStream_t st) {
     int rc;
-    gshared_ = shared_first_ ? gtrain : nullptr;
+    gshared_ = o_.shared_first ? gtrain : nullptr;
     for (const auto& b : blocks_opt_) {
       const Param& p = ps_[b.j];
       if (gshared_ && p.tap) continue;  // the first step reads the one copy in gtrain
@@ -455,8 +458,10 @@ class Net {
     return flush();
   }
 
-  // the dead-tap ranges of a training-order row, ascending (dead_ranges' table)
-  void dead_list(std::vector<std::pair<int64_t, int64_t>>& out) const {
+  // the dead-tap ranges (offset, length) of a training-order row, ascending:
+  // what a dead-tap parameter's live optimizer blocks leave uncovered
+  std::vector<std::pair<int64_t, int64_t>> dead_list() const {
+    std::vector<std::pair<int64_t, int64_t>> out;
     for (size_t j = 0; j < ps_.size(); ++j) {
       const Param& p = ps_[j];
       if (!p.dead) continue;
@@ -468,113 +473,169 @@ class Net {
       }
       if (p.n > e) out.push_back({p.off + e, p.n - e});
     }
+    return out;
   }
 
   // X's dead-tap ranges (training order) <- gtrain, rows k < nneg negated: one
   // launch over the range table when it fits and the rows are 16-B aligned
   // (was one broadcast per range: 57 launches per C3 round), else per range.
   int dead_ranges(const float* gtrain, float* X, int64_t ld, int64_t nneg, hipStream_t st) {
-    int rc;
-    DeadTable t;
-    t.cnt = 0;
-    int64_t total = 0;
-    bool fits = (reinterpret_cast<uintptr_t>(gtrain) & 15) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 &&
-                ld % 4 == 0 && K_ <= 65535;
-    for (size_t j = 0; j < ps_.size() && fits; ++j) {
-      const Param& p = ps_[j];
-      if (!p.dead) continue;
-      int64_t e = 0;
-      auto add = [&](int64_t a) {
-        if (a <= e) return;
-        if (t.cnt == DEAD_MAX) { fits = false; return; }
-        t.off[t.cnt] = p.off + e;
-        t.n[t.cnt++] = a - e;
-        total = std::max(total, a - e);
-      };
-      for (const auto& b : blocks_opt_) {
-        if (b.j != (int)j) continue;
-        add(b.o);
-        e = b.o + b.n;
-      }
-      add(p.n);
-    }
-    if (fits) {
-      if (t.cnt == 0) return FLR_OK;
-      const int64_t g = std::max<int64_t>(1, std::min<int64_t>(256, (total / 4 + THREADS - 1) / THREADS));
-      hipLaunchKernelGGL(dead_ranges_kernel, dim3((unsigned)g, (unsigned)K_), dim3(THREADS), 0, st, t, gtrain, X, ld,
-                         (int)std::min<int64_t>(nneg, K_));
-      return launch_status("train_clients: dead ranges");
-    }
-    for (size_t j = 0; j < ps_.size(); ++j) {
-      const Param& p = ps_[j];
-      if (!p.dead) continue;
-      int64_t e = 0;
-      auto fill = [&](int64_t a) {
-        if (a > e && (rc = flr_broadcast_rows_neg(gtrain + p.off + e, a - e, X + p.off + e, K_, ld, nneg, st)) !=
-                         FLR_OK)
+    const auto r = dead_list();
+    const bool fits = (reinterpret_cast<uintptr_t>(gtrain) & 15) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 &&
+                      ld % 4 == 0 && K_ <= 65535 && r.size() <= (size_t)DEAD_MAX;
+    if (!fits) {
+      int rc;
+      for (const auto& d : r)
+        if ((rc = flr_broadcast_rows_neg(gtrain + d.first, d.second, X + d.first, K_, ld, nneg, st)) != FLR_OK)
           return rc;
-        return (int)FLR_OK;
-      };
-      for (const auto& b : blocks_opt_) {
-        if (b.j != (int)j) continue;
-        if ((rc = fill(b.o)) != FLR_OK) return rc;
-        e = b.o + b.n;
-      }
-      if ((rc = fill(p.n)) != FLR_OK) return rc;
+      return FLR_OK;
     }
-    return FLR_OK;
+    if (r.empty()) return FLR_OK;
+    DeadTable t;
+    t.cnt = (int)r.size();
+    int64_t total = 0;  // the longest range
+    for (size_t i = 0; i < r.size(); ++i) {
+      t.off[i] = r[i].first;
+      t.n[i] = r[i].second;
+      total = std::max(total, r[i].second);
+    }
+    const int64_t g = std::max<int64_t>(1, std::min<int64_t>(256, (total / 4 + THREADS - 1) / THREADS));
+    hipLaunchKernelGGL(dead_ranges_kernel, dim3((unsigned)g, (unsigned)K_), dim3(THREADS), 0, st, t, gtrain, X, ld,
+                       (int)std::min<int64_t>(nneg, K_));
+    return launch_status("train_clients: dead ranges");
   }
 
-  // training order: the first step's tap-major conv weights are gshared_ (the
-  // global vector, one copy for every client; FLR_SHARED_FIRST=0: broadcast)
-  bool shared_first_ = true;
-  const float* gshared_ = nullptr;
-  bool first_ = false;
-  // the last step writes X's rows (training order) instead of the weights
-  float* xout_ = nullptr;
-  int64_t xld_ = 0, xneg_ = 0;
+  // What the entry point chooses for one training call: set once, before the
+  // first load or step.
+  struct Options {
+    AuxStream* side = nullptr;   // the optimizer's side stream (nullptr: the update runs on the caller's stream)
+    AuxStream* text = nullptr;   // the text branch's stream (nullptr: the caller's stream)
+    AuxStream* wgrad = nullptr;  // the weight-gradient stream (nullptr: on the caller's stream)
+    float* norms = nullptr;      // optional [K] clip norms (the caller's)
+    bool fuse_res = true;        // FLR_FUSED_RES=0: the separate gradient-sum pass (A/B)
+    // training order: the first step's tap-major conv weights are the global
+    // vector itself, one copy for every client (FLR_SHARED_FIRST=0: broadcast)
+    bool shared_first = true;
+    // training order: the last step writes X's rows instead of the weights
+    float* xout = nullptr;
+    int64_t xld = 0, xneg = 0;
+  };
+  void configure(const Options& o) { o_ = o; }
 
+  // One local step: its phases in the order they issue their launches.
   int step(const float* images, const int64_t* tokens, const int64_t* labels, const float* mask, bool first,
            bool last, float* loss_row, float lr, float mom, hipStream_t st) {
     int rc;
-#define FLR_TRY(x) \
-  if ((rc = (x)) != FLR_OK) return rc
-    const auto& s = s_;
-    const int64_t C0 = s.in_channels, HW0 = s.image_size * s.image_size, N = B_ * T_;
-    first_ = first;
-    // ---------------- forward ----------------
+    const int64_t C0 = s_.in_channels, HW0 = s_.image_size * s_.image_size;
+    const Param& whh = ps_[p_whh_];
+    Step S;
+    S.st = st;
+    // the text branch on its own stream beside the trunk (AUX_TEXT, side_stream.h);
+    // its workspaces (gws_, rws_, ews_) are not used by the trunk
+    S.conc = o_.text != nullptr;
+    S.ts = S.conc ? o_.text->s : st;
+    S.first = first;
+    S.last = last;
+    S.fused = B_ <= 32;
+    // the whole recurrence in one launch per pass where the shape allows and K is
+    // large enough for it to pay (FLR_GRU_SEQ=0: per step; =1: wherever eligible)
+    S.seq = S.fused && flr_gru_seq_preferred(K_, B_, T_, H_) != 0;
+    // first step in training order: one copy of the global tap-major conv weights
+    // and one packed copy of the global W_hh for every client
+    S.wsh = first && gshared_ != nullptr;
+    S.whh = S.wsh ? gshared_ + whh.off : whh.w;
+    S.whh_n = S.wsh ? 1 : K_;
+    S.wg = {o_.wgrad, 0};
+    S.tx = {o_.text, TX_WG_FORK0};
     hipLaunchKernelGGL(permute_images_kernel, dim3(grid_for(K_ * B_ * C0 * HW0)), dim3(THREADS), 0, st, images,
                        ximg_, K_, B_, C0, HW0);
     FLR_TRY(launch_status("train_clients: images"));
     // the text branch first: its recurrence is latency-bound, so the previous step's
     // side-stream update of the trunk (HBM-bound) runs under it (side_stream.h)
-    const Param &emb = ps_[p_emb_], &wih = ps_[p_wih_], &whh = ps_[p_whh_], &bih = ps_[p_bih_],
-                &bhh = ps_[p_bhh_], &w1 = ps_[p_w1_], &b1 = ps_[p_b1_], &w2 = ps_[p_w2_], &b2 = ps_[p_b2_];
-    // the text branch on its own stream beside the trunk (text_stream, side_stream.h);
-    // its workspaces (gws_, rws_, ews_) are not used by the trunk
-    const bool conc = text_ != nullptr;
-    const hipStream_t ts = conc ? text_->s : st;
-    if (conc) FLR_TRY(fork(st, ts, 0));
+    FLR_TRY(text_forward(S, tokens));
+    FLR_TRY(trunk_forward(S));
+    FLR_TRY(head_forward(S, labels, mask, loss_row));
+    // the weight-gradient stream: forks from here on, again from its first event
+    // (every side-stream update of the previous step was joined before the head,
+    // so no update still reads p.g)
+    S.wg = {o_.wgrad, 0};
+    FLR_TRY(head_backward(S, mask));
+    FLR_TRY(text_backward(S, tokens));
+    FLR_TRY(trunk_backward(S));
+    FLR_TRY(join_backward(S));
+    return optimizer(S, lr, mom);
+  }
+
+  // client-matrix rows in torch order (export), rows k < nneg negated
+  int export_rows(float* X, int64_t ld, int64_t nneg, hipStream_t st) {
+    int rc;
+    for (auto& p : ps_) {
+      if (p.tap)
+        rc = flr_tap_major_to_torch_neg(p.w, K_, p.shape[2] * p.shape[3], p.shape[1], p.shape[0], X + p.off, ld, nneg,
+                                        st);
+      else
+        rc = flr_copy_rows_neg(p.w, p.n, p.n, X + p.off, ld, K_, nneg, st);
+      if (rc != FLR_OK) return rc;
+    }
+    return FLR_OK;
+  }
+
+  int64_t live_params() const {
+    int64_t n = 0;
+    for (const auto& b : blocks_opt_) n += b.n;
+    return n;
+  }
+
+ private:
+  struct OptBlock {
+    int j;
+    int64_t o, n, cs;
+  };
+
+  // the text stream's events
+  enum TextEvent {
+    TX_FWD_FORK = 0,  // the caller's stream -> the text forward
+    TX_FWD_JOIN,      // the text forward -> the head (recorded after the GRU, waited on before fc1)
+    TX_BWD_FORK,      // the head's backward -> the text backward
+    TX_BWD_JOIN,      // the text backward -> the joins before the optimizer
+    TX_WG_FORK0,      // first of the forks of the trunk's last weight gradients onto the idle text stream
+    TX_WG_JOIN = kAuxEvents[AUX_TEXT] - 1,  // their join
+  };
+
+  // what one step's phases share
+  struct Step {
+    hipStream_t st = nullptr, ts = nullptr;  // the caller's stream; the text branch's (st without a text stream)
+    bool conc = false;                       // the text branch runs on its own stream
+    bool first = false, last = false;
+    bool fused = false, seq = false;  // the GRU's form: fused per step; the whole recurrence in one launch
+    bool wsh = false;                 // tap-major conv weights and W_hh read the one shared global copy
+    const float* whh = nullptr;       // W_hh as the GRU's pack reads it, and its client count
+    int64_t whh_n = 0;
+    EventCursor wg;           // the weight-gradient stream's next event (shortcut forks, then weight-gradient forks)
+    EventCursor tx;           // the text stream's next weight-gradient fork event
+    bool wg_on_text = false;  // this conv's dW on the text stream (the first FLR_WG_TEXT residual blocks)
+  };
+
+  // ---------------- forward ----------------
+  int text_forward(const Step& S, const int64_t* tokens) {
+    int rc;
+    const Param &emb = ps_[p_emb_], &wih = ps_[p_wih_], &whh = ps_[p_whh_], &bih = ps_[p_bih_], &bhh = ps_[p_bhh_];
+    const int64_t N = B_ * T_, H3 = 3 * H_;
+    const hipStream_t ts = S.ts;
+    if (S.conc) FLR_TRY(ev_link(o_.text->ev[TX_FWD_FORK], S.st, ts, "train_clients: text-stream fork"));
     FLR_TRY(wait_group(gtext_, ts));
-    FLR_TRY(flr_embedding_fwd(emb.w, s.vocab * E_, s.vocab, tokens, N, nullptr, 0, 0, nullptr, 0, nullptr, 0, 0,
+    FLR_TRY(flr_embedding_fwd(emb.w, s_.vocab * E_, s_.vocab, tokens, N, nullptr, 0, 0, nullptr, 0, nullptr, 0, 0,
                               nullptr, 0, K_, N, E_, emb_, ts));
-    const int64_t H3 = 3 * H_;
     FLR_TRY(gemm(emb_, N * E_, E_, 1, wih.w, H3 * E_, E_, 1, gi_, N * H3, H3, 1, bih.w, H3, nullptr, N, H3, E_, ts));
-    const bool fused = B_ <= 32;
-    // first step in training order: one packed copy of the global W_hh for every client
-    const bool wsh = first_ && gshared_ != nullptr;
-    // the whole recurrence in one launch per pass where the shape allows and K is
-    // large enough for it to pay (FLR_GRU_SEQ=0: per step; =1: wherever eligible)
-    const bool seq = fused && flr_gru_seq_preferred(K_, B_, T_, H_) != 0;
-    if (seq) {
+    if (S.seq) {
       FLR_TRY(flr_gru_zero_h0(hseq_, K_, B_, T_, H_, ts));  // the launch writes every later slot
-      FLR_TRY(flr_gru_pack(wsh ? gshared_ + whh.off : whh.w, wsh ? 1 : K_, 3, H_, H_, 0, whhP_, ts));
-      FLR_TRY(flr_gru_fwd_seq(gi_, whhP_, wsh ? 1 : 0, bhh.w, hseq_, gates_, K_, B_, T_, H_, ts));
-    } else if (fused) {
+      FLR_TRY(flr_gru_pack(S.whh, S.whh_n, 3, H_, H_, 0, whhP_, ts));
+      FLR_TRY(flr_gru_fwd_seq(gi_, whhP_, S.wsh, bhh.w, hseq_, gates_, K_, B_, T_, H_, ts));
+    } else if (S.fused) {
       FLR_TRY(flr_fill(hseq_, K_ * (T_ + 1) * B_ * H_, 0.f, ts));
-      FLR_TRY(flr_gru_pack(wsh ? gshared_ + whh.off : whh.w, wsh ? 1 : K_, 3, H_, H_, 0, whhP_, ts));
+      FLR_TRY(flr_gru_pack(S.whh, S.whh_n, 3, H_, H_, 0, whhP_, ts));
       for (int64_t t = 0; t < T_; ++t)
-        FLR_TRY(flr_gru_fwd_fused_ex(gi_, whhP_, wsh ? 1 : 0, bhh.w, hseq_, gates_, K_, B_, T_, H_, t, ts));
+        FLR_TRY(flr_gru_fwd_fused_ex(gi_, whhP_, S.wsh, bhh.w, hseq_, gates_, K_, B_, T_, H_, t, ts));
     } else {
       FLR_TRY(flr_fill(hseq_, K_ * (T_ + 1) * B_ * H_, 0.f, ts));
       for (int64_t t = 0; t < T_; ++t) {
@@ -583,51 +644,61 @@ class Net {
         FLR_TRY(flr_gru_fwd_step(gi_, gh_, hseq_, gates_, K_, B_, T_, H_, t, ts));
       }
     }
-    if (conc) FLR_TRY(fork(ts, st, 1));  // joined before the head (event recorded here, waited there)
+    // joined before the head (event recorded here, waited on there)
+    if (S.conc) FLR_TRY(ev_record(o_.text->ev[TX_FWD_JOIN], ts, "train_clients: text-stream event"));
+    return FLR_OK;
+  }
+
+  int trunk_forward(Step& S) {
+    int rc;
+    const hipStream_t st = S.st;
     int seg = 0;  // the previous step's update of each trunk segment's parameters (side stream)
     FLR_TRY(wait_group(seg++, st));
-    FLR_TRY(conv_fwd(stem_, ximg_, y0_, st));
+    FLR_TRY(conv_fwd(S, stem_, ximg_, y0_, st));
     if (stem_fused_) {  // bn1 + relu + maxpool in one pass: the BN output never reaches HBM
       FLR_TRY(flr_batchnorm_relu_maxpool_fwd(y0_, ps_[stem_bn_.pg].w, ps_[stem_bn_.pb].w, p0_, arg0_, stem_bn_.mean,
-                                             stem_bn_.invstd, K_ * s.widths[0], B_, Hs_, Hs_, 1e-5f, st));
+                                             stem_bn_.invstd, K_ * s_.widths[0], B_, Hs_, Hs_, 1e-5f, st));
     } else {
       FLR_TRY(bn_fwd(stem_bn_, y0_, nullptr, a0_, true, st));
-      FLR_TRY(flr_maxpool2d_fwd(a0_, p0_, arg0_, K_ * s.widths[0] * B_, Hs_, Hs_, 3, 3, 2, 1, st));
+      FLR_TRY(flr_maxpool2d_fwd(a0_, p0_, arg0_, K_ * s_.widths[0] * B_, Hs_, Hs_, 3, 3, 2, 1, st));
     }
     // a block's shortcut (strided 1x1 conv + BN) on the weight-gradient stream, idle in
     // the forward, beside conv1 / bn1 / conv2; joined before bn2 adds it
-    int fev = 0;
     for (auto& bk : blocks_) {
       const float* idt = bk.x_in;
       FLR_TRY(wait_group(seg++, st));
-      const bool ds_side = bk.has_ds && wgs_ && fev + 2 <= WgradStream::NEV;
+      const bool ds_side = bk.has_ds && S.wg.left(2);  // its fork and its join
+      hipEvent_t ds_done = nullptr;
       if (bk.has_ds) {
-        const hipStream_t dst = ds_side ? wgs_->s : st;
-        if (ds_side && (hipEventRecord(wgs_->ev[fev], st) != hipSuccess ||
-                        hipStreamWaitEvent(dst, wgs_->ev[fev], 0) != hipSuccess))
-          return launch_status("train_clients: shortcut fork");
-        FLR_TRY(conv_fwd(bk.ds, bk.x_in, bk.yd, dst, ds_side ? cws2_ : nullptr));
+        const hipStream_t dst = ds_side ? o_.wgrad->s : st;
+        if (ds_side) FLR_TRY(ev_link(S.wg.take(), st, dst, "train_clients: shortcut fork"));
+        FLR_TRY(conv_fwd(S, bk.ds, bk.x_in, bk.yd, dst, ds_side ? cws2_ : nullptr));
         FLR_TRY(bn_fwd(bk.bds, bk.yd, nullptr, bk.ad, false, dst));
-        if (ds_side && hipEventRecord(wgs_->ev[fev + 1], dst) != hipSuccess)
-          return launch_status("train_clients: shortcut event");
+        if (ds_side) {
+          ds_done = S.wg.take();
+          FLR_TRY(ev_record(ds_done, dst, "train_clients: shortcut event"));
+        }
         idt = bk.ad;
       }
-      FLR_TRY(conv_fwd(bk.c1, bk.x_in, bk.y1, st));
+      FLR_TRY(conv_fwd(S, bk.c1, bk.x_in, bk.y1, st));
       FLR_TRY(bn_fwd(bk.b1, bk.y1, nullptr, bk.a1, true, st));
-      FLR_TRY(conv_fwd(bk.c2, bk.a1, bk.y2, st));
-      if (ds_side) {
-        if (hipStreamWaitEvent(st, wgs_->ev[fev + 1], 0) != hipSuccess)
-          return launch_status("train_clients: shortcut join");
-        fev += 2;
-      }
+      FLR_TRY(conv_fwd(S, bk.c2, bk.a1, bk.y2, st));
+      if (ds_side) FLR_TRY(ev_wait(st, ds_done, "train_clients: shortcut join"));
       FLR_TRY(bn_fwd(bk.b2, bk.y2, idt, bk.out, true, st));
     }
-    const float* x4 = blocks_.back().out;  // [K][Dimg][B]: img[k][b][c] = x4[k][c][b]
+    return FLR_OK;
+  }
+
+  // fc1 over the column blocks [img | h] (never concatenated), ReLU + dropout mask
+  // in the epilogue; fc2; the loss
+  int head_forward(const Step& S, const int64_t* labels, const float* mask, float* loss_row) {
+    int rc;
+    const Param &w1 = ps_[p_w1_], &b1 = ps_[p_b1_], &w2 = ps_[p_w2_], &b2 = ps_[p_b2_];
+    const hipStream_t st = S.st;
+    const float* x4 = blocks_.back().out;    // [K][Dimg][B]: img[k][b][c] = x4[k][c][b]
     const float* hT = hseq_ + T_ * B_ * H_;  // [K][B][H] at client stride (T+1)*B*H
     const int64_t hk = (T_ + 1) * B_ * H_, DI = Dimg_ + H_;
-    // fc1 over the column blocks [img | h] (never concatenated), ReLU + dropout mask in the epilogue
-    if (conc && hipStreamWaitEvent(st, text_->ev[1], 0) != hipSuccess)
-      return launch_status("train_clients: text-stream join");
+    if (S.conc) FLR_TRY(ev_wait(st, o_.text->ev[TX_FWD_JOIN], "train_clients: text-stream join"));
     FLR_TRY(wait_group(ghead_, st));
     pending_ = false;  // every side-stream update of the previous step is joined
     FLR_TRY(flr_bgemm_ex(x4, Dimg_ * B_, 1, B_, w1.w, F_ * DI, DI, 1, h1_, B_ * F_, F_, 1, b1.w, F_, nullptr,
@@ -637,13 +708,18 @@ class Net {
     FLR_TRY(gemm(h1_, B_ * F_, F_, 1, w2.w, C_ * F_, F_, 1, logits_, B_ * C_, C_, 1, b2.w, C_, nullptr, B_, C_, F_,
                  st));
     FLR_TRY(flr_cross_entropy(logits_, labels, K_, B_, C_, loss_, dlogits_, rows_, st));
-    FLR_TRY(flr_copy_rows(loss_, K_, K_, loss_row, K_, 1, st));
-    // ---------------- backward ----------------
-    // the weight-gradient stream: forks from here on (every side-stream update of
-    // the previous step was joined before the head, so no update still reads p.g)
-    WgradStream* wgs_save = wgs_;
-    wev_ = 0;
-    // head (ClientMLP.backward): dpre = dlogits W2 * relu'(h1) * mask
+    return flr_copy_rows(loss_, K_, K_, loss_row, K_, 1, st);
+  }
+
+  // ---------------- backward ----------------
+  // head (ClientMLP.backward): dpre = dlogits W2 * relu'(h1) * mask
+  int head_backward(const Step& S, const float* mask) {
+    int rc;
+    const Param &w1 = ps_[p_w1_], &b1 = ps_[p_b1_], &w2 = ps_[p_w2_], &b2 = ps_[p_b2_];
+    const hipStream_t st = S.st;
+    const float* x4 = blocks_.back().out;
+    const float* hT = hseq_ + T_ * B_ * H_;
+    const int64_t hk = (T_ + 1) * B_ * H_, DI = Dimg_ + H_;
     FLR_TRY(flr_bgemm_ex(dlogits_, B_ * C_, C_, 1, w2.w, C_ * F_, 1, F_, dpre_, B_ * F_, F_, 1, nullptr, 0, nullptr,
                          FLR_ACT_DRELU, mask, h1_, nullptr, K_, B_, F_, C_, gws_, gws_n_, st));
     FLR_TRY(gemm(dlogits_, B_ * C_, 1, C_, h1_, B_ * F_, 1, F_, w2.g, C_ * F_, F_, 1, nullptr, 0, nullptr, C_, F_, B_,
@@ -658,19 +734,25 @@ class Net {
                  F_, st));
     FLR_TRY(gemm(dpre_, B_ * F_, 1, F_, hT, hk, 1, H_, w1.g + Dimg_, F_ * DI, DI, 1, nullptr, 0, nullptr, F_, H_, B_,
                  st));
-    FLR_TRY(rowsum(dpre_, B_ * F_, F_, B_, F_, b1.g, st));
-    if (conc) FLR_TRY(fork(st, ts, 2));
-    // GRU (ClientGRU.backward)
-    if (seq) {
-      FLR_TRY(flr_gru_pack(wsh ? gshared_ + whh.off : whh.w, wsh ? 1 : K_, 1, H_, H3, 1, whhT_, ts));
-      FLR_TRY(flr_gru_bwd_seq(whhT_, wsh ? 1 : 0, gates_, hseq_, dh_, dgh_, dgi_, dh_direct_, nullptr, K_, B_, T_, H_,
-                              ts));
-    } else if (fused) {
-      FLR_TRY(flr_gru_pack(wsh ? gshared_ + whh.off : whh.w, wsh ? 1 : K_, 1, H_, H3, 1, whhT_, ts));
+    return rowsum(dpre_, B_ * F_, F_, B_, F_, b1.g, st);
+  }
+
+  // GRU (ClientGRU.backward), W_ih (ClientLinear.backward), then the embedding
+  int text_backward(const Step& S, const int64_t* tokens) {
+    int rc;
+    const Param &emb = ps_[p_emb_], &wih = ps_[p_wih_], &whh = ps_[p_whh_], &bih = ps_[p_bih_], &bhh = ps_[p_bhh_];
+    const int64_t N = B_ * T_, H3 = 3 * H_, hk = (T_ + 1) * B_ * H_;
+    const hipStream_t ts = S.ts;
+    if (S.conc) FLR_TRY(ev_link(o_.text->ev[TX_BWD_FORK], S.st, ts, "train_clients: text-stream fork"));
+    if (S.seq) {
+      FLR_TRY(flr_gru_pack(S.whh, S.whh_n, 1, H_, H3, 1, whhT_, ts));
+      FLR_TRY(flr_gru_bwd_seq(whhT_, S.wsh, gates_, hseq_, dh_, dgh_, dgi_, dh_direct_, nullptr, K_, B_, T_, H_, ts));
+    } else if (S.fused) {
+      FLR_TRY(flr_gru_pack(S.whh, S.whh_n, 1, H_, H3, 1, whhT_, ts));
       FLR_TRY(flr_gru_bwd_step(dh_, gates_, hseq_, dgh_, dgi_, dh_direct_, K_, B_, T_, H_, T_ - 1, ts));
       for (int64_t t = T_ - 1; t > 0; --t)
-        FLR_TRY(flr_gru_bwd_fused_ex(whhT_, wsh ? 1 : 0, gates_, hseq_, dgh_, dgi_, dh_direct_, nullptr, K_, B_, T_,
-                                     H_, t, ts));
+        FLR_TRY(flr_gru_bwd_fused_ex(whhT_, S.wsh, gates_, hseq_, dgh_, dgi_, dh_direct_, nullptr, K_, B_, T_, H_, t,
+                                     ts));
     } else {
       const float* dh = dh_;
       for (int64_t t = T_ - 1; t >= 0; --t) {
@@ -686,48 +768,52 @@ class Net {
     FLR_TRY(gemm(dgh_, T_ * B_ * H3, 1, H3, hseq_, hk, 1, H_, whh.g, H3 * H_, H_, 1, nullptr, 0, nullptr, H3, H_,
                  T_ * B_, ts));
     FLR_TRY(rowsum(dgh_, T_ * B_ * H3, H3, T_ * B_, H3, bhh.g, ts));
-    // W_ih (ClientLinear.backward), then the embedding
     FLR_TRY(gemm(dgi_, N * H3, H3, 1, wih.w, H3 * E_, 1, E_, demb_, N * E_, E_, 1, nullptr, 0, nullptr, N, E_, H3, ts));
     FLR_TRY(gemm(dgi_, N * H3, 1, H3, emb_, N * E_, 1, E_, wih.g, H3 * E_, E_, 1, nullptr, 0, nullptr, H3, E_, N, ts));
     FLR_TRY(rowsum(dgi_, N * H3, H3, N, H3, bih.g, ts));
-    FLR_TRY(flr_embedding_bwd(demb_, tokens, N, K_, N, s.vocab, E_, emb.g, s.vocab * E_, 1, ews_, ews_n_, ts));
-    if (sq_early_base_ >= 0) FLR_TRY(early_sumsq(ts));  // the head's gradients: on st before fork 2
-    if (conc) FLR_TRY(fork(ts, st, 3));
-    // trunk, last block first.  The first blocks' weight gradients come last,
-    // behind the weight-gradient stream's backlog, when the text stream has long
-    // been idle: they run there instead (FLR_WG_TEXT blocks; 0: off)
-    const int wg_text = conc ? [] {
+    FLR_TRY(flr_embedding_bwd(demb_, tokens, N, K_, N, s_.vocab, E_, emb.g, s_.vocab * E_, 1, ews_, ews_n_, ts));
+    if (sq_early_base_ >= 0) FLR_TRY(early_sumsq(ts));  // the head's gradients: on st before TX_BWD_FORK
+    if (S.conc) FLR_TRY(ev_record(o_.text->ev[TX_BWD_JOIN], ts, "train_clients: text-stream event"));
+    return FLR_OK;
+  }
+
+  // trunk, last block first.  The first blocks' weight gradients come last,
+  // behind the weight-gradient stream's backlog, when the text stream has long
+  // been idle: they run there instead (FLR_WG_TEXT blocks; 0: off)
+  int trunk_backward(Step& S) {
+    int rc;
+    const hipStream_t st = S.st;
+    const int wg_text = S.conc ? [] {
       const char* e = flr::knob("FLR_WG_TEXT");
       return e ? atoi(e) : 2;
     }() : 0;
-    tev_ = 4;
     for (int bi = (int)blocks_.size() - 1; bi >= 0; --bi) {
       Block& bk = blocks_[bi];
-      wg_on_text_ = bi < wg_text;
+      S.wg_on_text = bi < wg_text;
       const float* d_out = bi + 1 < (int)blocks_.size() ? blocks_[bi + 1].d_in : d_x4_;
       FLR_TRY(bn_bwd(bk.b2, d_out, bk.y2, bk.out, true, bk.d_y2, bk.d_res, st));
-      FLR_TRY(conv_bwd(bk.c2, bk.a1, bk.d_y2, bk.d_a1, st));
+      FLR_TRY(conv_bwd(S, bk.c2, bk.a1, bk.d_y2, bk.d_a1, st));
       FLR_TRY(bn_bwd(bk.b1, bk.d_a1, bk.y1, bk.a1, true, bk.d_y1, nullptr, st));
       const float* other = bk.d_res;  // identity shortcut: the residual gradient itself
       if (bk.has_ds) {
         FLR_TRY(bn_bwd(bk.bds, bk.d_res, bk.yd, nullptr, false, bk.d_yd, nullptr, st));
-        if (ps_[bk.c1.p].tap && ps_[bk.ds.p].tap && fuse_res_) {
+        if (ps_[bk.c1.p].tap && ps_[bk.ds.p].tap && o_.fuse_res) {
           // d_in = dgrad(c1), then the strided 1x1 shortcut's dgrad added in place
           // (its epilogue: dx = dgrad(ds) + dx, the same one fp32 add); the parity
           // classes no shortcut tap reaches are skipped instead of written as zeros
-          FLR_TRY(conv_bwd(bk.c1, bk.x_in, bk.d_y1, bk.d_in, st));
-          FLR_TRY(conv_bwd(bk.ds, bk.x_in, bk.d_yd, bk.d_in, st, bk.d_in));
+          FLR_TRY(conv_bwd(S, bk.c1, bk.x_in, bk.d_y1, bk.d_in, st));
+          FLR_TRY(conv_bwd(S, bk.ds, bk.x_in, bk.d_yd, bk.d_in, st, bk.d_in));
           continue;
         }
-        FLR_TRY(conv_bwd(bk.ds, bk.x_in, bk.d_yd, bk.d_xd, st));
+        FLR_TRY(conv_bwd(S, bk.ds, bk.x_in, bk.d_yd, bk.d_xd, st));
         other = bk.d_xd;
       }
       // d_in = dgrad(c1) + other: the two paths' sum (autograd's accumulation),
       // in the dgrad epilogue when c1 is tap-major, else one extra pass
-      if (ps_[bk.c1.p].tap && fuse_res_) {
-        FLR_TRY(conv_bwd(bk.c1, bk.x_in, bk.d_y1, bk.d_in, st, other));
+      if (ps_[bk.c1.p].tap && o_.fuse_res) {
+        FLR_TRY(conv_bwd(S, bk.c1, bk.x_in, bk.d_y1, bk.d_in, st, other));
       } else {
-        FLR_TRY(conv_bwd(bk.c1, bk.x_in, bk.d_y1, bk.d_xm, st));
+        FLR_TRY(conv_bwd(S, bk.c1, bk.x_in, bk.d_y1, bk.d_xm, st));
         hipLaunchKernelGGL(add_kernel, dim3(grid_for(bk.in_elems)), dim3(THREADS), 0, st, bk.d_xm, other, bk.d_in,
                            bk.in_elems);
         FLR_TRY(launch_status("train_clients: gradient sum"));
@@ -736,27 +822,37 @@ class Net {
     if (stem_fused_) {
       FLR_TRY(flr_maxpool_relu_batchnorm_bwd(d_p0_, arg0_, y0_, ps_[stem_bn_.pg].w, ps_[stem_bn_.pb].w, stem_bn_.mean,
                                              stem_bn_.invstd, d_y0_, ps_[stem_bn_.pg].g, ps_[stem_bn_.pb].g,
-                                             K_ * s.widths[0], B_, Hs_, Hs_, st));
+                                             K_ * s_.widths[0], B_, Hs_, Hs_, st));
     } else {
-      FLR_TRY(flr_maxpool2d_bwd(d_p0_, arg0_, d_a0_, K_ * s.widths[0] * B_, Hs_, Hs_, 3, 3, 2, 1, st));
+      FLR_TRY(flr_maxpool2d_bwd(d_p0_, arg0_, d_a0_, K_ * s_.widths[0] * B_, Hs_, Hs_, 3, 3, 2, 1, st));
       FLR_TRY(bn_bwd(stem_bn_, d_a0_, y0_, a0_, true, d_y0_, nullptr, st));
     }
-    wg_on_text_ = false;
-    FLR_TRY(conv_bwd(stem_, ximg_, d_y0_, nullptr, st));
-    if (conc && hipStreamWaitEvent(st, text_->ev[3], 0) != hipSuccess)
-      return launch_status("train_clients: text-stream join");
-    if (conc && tev_ > 4) {  // the weight gradients run on the text stream
-      if (hipEventRecord(text_->ev[TextStream::NEV - 1], text_->s) != hipSuccess ||
-          hipStreamWaitEvent(st, text_->ev[TextStream::NEV - 1], 0) != hipSuccess)
-        return launch_status("train_clients: text-stream weight-gradient join");
+    S.wg_on_text = false;
+    return conv_bwd(S, stem_, ximg_, d_y0_, nullptr, st);
+  }
+
+  // every branch of the backward back into the caller's stream, before the clip:
+  // the text backward, the weight gradients forked onto the text stream, and the
+  // weight-gradient stream's (with their clip-norm partials)
+  int join_backward(Step& S) {
+    int rc;
+    const hipStream_t st = S.st;
+    if (S.conc) FLR_TRY(ev_wait(st, o_.text->ev[TX_BWD_JOIN], "train_clients: text-stream join"));
+    if (S.conc && S.tx.next > TX_WG_FORK0)
+      FLR_TRY(ev_link(o_.text->ev[TX_WG_JOIN], o_.text->s, st, "train_clients: text-stream weight-gradient join"));
+    if (o_.wgrad && S.wg.next > 0) {
+      if (!S.wg.left(1)) return FLR_ERR_UNSUPPORTED;
+      FLR_TRY(ev_link(S.wg.take(), o_.wgrad->s, st, "train_clients: weight-gradient join"));
     }
-    if (wgs_ && wev_ > 0) {  // every weight gradient (and its clip-norm partials) before the clip
-      if (wev_ >= WgradStream::NEV) return FLR_ERR_UNSUPPORTED;
-      if (hipEventRecord(wgs_->ev[wev_], wgs_->s) != hipSuccess || hipStreamWaitEvent(st, wgs_->ev[wev_], 0) != hipSuccess)
-        return launch_status("train_clients: weight-gradient join");
-    }
-    wgs_ = wgs_save;
-    // ---------------- clip + SGD-momentum ----------------
+    return FLR_OK;
+  }
+
+  // ---------------- clip + SGD-momentum ----------------
+  int optimizer(const Step& S, float lr, float mom) {
+    int rc;
+    const hipStream_t st = S.st;
+    const bool first = S.first, last = S.last;
+    AuxStream* const side = o_.side;
     std::vector<float*> xb, mb;
     std::vector<const float*> gb;
     std::vector<int64_t> nb, cs;
@@ -775,31 +871,28 @@ class Net {
     const bool fuse = clip_ > 0 && nsq_ > 0;
     // first step in training order: the tap-major blocks read the shared global copy
     std::vector<int64_t> soffs;
-    const bool src = first && gshared_;
+    const bool src = S.wsh;
     if (src)
       for (const auto& b : blocks_opt_) soffs.push_back(ps_[b.j].tap ? ps_[b.j].off + b.o : -1);
     const int flags = int(first) | (int(last) << 1);
     // the last step writes X: nothing after it in the call to overlap; a model with
     // more parameter groups than the side stream has events updates on the caller's stream
-    if (last || !side_ || (int)gthr_.size() + 1 > SideStream::NEV) {
-      FLR_TRY(flr_clip_sgd_step_blocked_src(xb.data(), gb.data(), mb.data(), nb.data(), cs.data(),
-                                            (int64_t)xb.size(), K_, lr, mom, wd_, clip_, flags, last ? xout_ : nullptr,
-                                            last && xout_ ? xoffs.data() : nullptr, xld_, xneg_,
-                                            fuse ? normed.data() : nullptr, fuse ? sq_ : nullptr, fuse ? nsq_ : 0,
-                                            src ? gshared_ : nullptr, src ? soffs.data() : nullptr, norms_, sgd_ws_,
-                                            sgd_ws_n_, st));
-      return FLR_OK;
+    if (last || !side || (int)gthr_.size() + 1 > side->nev) {
+      return flr_clip_sgd_step_blocked_src(xb.data(), gb.data(), mb.data(), nb.data(), cs.data(), (int64_t)xb.size(),
+                                           K_, lr, mom, wd_, clip_, flags, last ? o_.xout : nullptr,
+                                           last && o_.xout ? xoffs.data() : nullptr, o_.xld, o_.xneg,
+                                           fuse ? normed.data() : nullptr, fuse ? sq_ : nullptr, fuse ? nsq_ : 0,
+                                           src ? gshared_ : nullptr, src ? soffs.data() : nullptr, o_.norms, sgd_ws_,
+                                           sgd_ws_n_, st);
     }
     // the clip norms on this stream; the update on the side stream, one launch per
     // forward segment's parameter group, each followed by its event (wait_group)
     FLR_TRY(flr_clip_sgd_step_phase(xb.data(), gb.data(), mb.data(), nb.data(), cs.data(), (int64_t)xb.size(), K_, lr,
                                     mom, wd_, clip_, flags, nullptr, nullptr, 0, 0, fuse ? normed.data() : nullptr,
-                                    fuse ? sq_ : nullptr, fuse ? nsq_ : 0, nullptr, nullptr, norms_,
+                                    fuse ? sq_ : nullptr, fuse ? nsq_ : 0, nullptr, nullptr, o_.norms,
                                     FLR_SGD_PHASE_NORM, sgd_ws_, sgd_ws_n_, st));
-    const int ng = (int)gthr_.size();
-    hipEvent_t fork = side_->ev[ng];
-    if (hipEventRecord(fork, st) != hipSuccess || hipStreamWaitEvent(side_->s, fork, 0) != hipSuccess)
-      return launch_status("train_clients: side-stream fork");
+    const int ng = (int)gthr_.size();  // the groups' events come first, the fork's after them
+    FLR_TRY(ev_link(side->ev[ng], st, side->s, "train_clients: side-stream fork"));
     // group g = the blocks of parameters [gthr_[g-1], gthr_[g]); launched in forward order
     // (text branch, stem, residual blocks, head), each followed by its event
     size_t nlaunched = 0;
@@ -815,24 +908,19 @@ class Net {
         FLR_TRY(flr_clip_sgd_step_phase(sub(xb), sub(gb), sub(mb), sub(nb), sub(cs), (int64_t)(i1 - i0), K_, lr, mom,
                                         wd_, clip_, flags, nullptr, nullptr, 0, 0, nullptr, nullptr, 0,
                                         src ? gshared_ : nullptr, src ? sub(soffs) : nullptr, nullptr,
-                                        FLR_SGD_PHASE_UPDATE, sgd_ws_, sgd_ws_n_, side_->s));
+                                        FLR_SGD_PHASE_UPDATE, sgd_ws_, sgd_ws_n_, side->s));
       }
-      if (hipEventRecord(side_->ev[g], side_->s) != hipSuccess) return launch_status("train_clients: side-stream event");
+      FLR_TRY(ev_record(side->ev[g], side->s, "train_clients: side-stream event"));
     }
     if (nlaunched != blocks_opt_.size()) return FLR_ERR_ARG;  // a block outside every group: parameters out of order
     pending_ = true;
-#undef FLR_TRY
     return FLR_OK;
   }
 
   // the forward's wait for the previous step's side-stream update of group g
-  // record event e on `from`; with e even, `to` waits on it now (a fork); odd
-  // events are waited on later by the caller (a join)
-  int fork(hipStream_t from, hipStream_t to, int e) {
-    if (hipEventRecord(text_->ev[e], from) != hipSuccess) return launch_status("train_clients: text-stream event");
-    if (!(e & 1) && hipStreamWaitEvent(to, text_->ev[e], 0) != hipSuccess)
-      return launch_status("train_clients: text-stream fork");
-    return FLR_OK;
+  int wait_group(int g, hipStream_t st) {
+    if (!pending_) return FLR_OK;
+    return ev_wait(st, o_.side->ev[g], "train_clients: side-stream join");
   }
 
   // the clip-norm partials of the parameters marked sq_early (their optimizer
@@ -851,40 +939,6 @@ class Net {
     return clip_sumsq_blocks(g.data(), n.data(), cs.data(), (int64_t)g.size(), K_, sq_ + sq_early_base_, nsq_,
                              kEarlySlots, s);
   }
-
-  int wait_group(int g, hipStream_t st) {
-    if (!pending_) return FLR_OK;
-    if (hipStreamWaitEvent(st, side_->ev[g], 0) != hipSuccess) return launch_status("train_clients: side-stream join");
-    return FLR_OK;
-  }
-
-  // client-matrix rows in torch order (export), rows k < nneg negated
-  int export_rows(float* X, int64_t ld, int64_t nneg, hipStream_t st) {
-    int rc;
-    for (auto& p : ps_) {
-      if (p.tap)
-        rc = flr_tap_major_to_torch_neg(p.w, K_, p.shape[2] * p.shape[3], p.shape[1], p.shape[0], X + p.off, ld, nneg,
-                                        st);
-      else
-        rc = flr_copy_rows_neg(p.w, p.n, p.n, X + p.off, ld, K_, nneg, st);
-      if (rc != FLR_OK) return rc;
-    }
-    return FLR_OK;
-  }
-
-  float* norms_ = nullptr;  // optional [K] clip norms (the caller's)
-  bool fuse_res_ = true;     // FLR_FUSED_RES=0: the separate gradient-sum pass (A/B)
-  int64_t live_params() const {
-    int64_t n = 0;
-    for (const auto& b : blocks_opt_) n += b.n;
-    return n;
-  }
-
- private:
-  struct OptBlock {
-    int j;
-    int64_t o, n, cs;
-  };
 
   template <class T>
   T* alloc(int64_t n) {
@@ -948,45 +1002,41 @@ class Net {
 
   // a tap-major conv weight: per client, or (first step, training order) the
   // one global copy every client reads with client stride 0
-  const float* tap_w(const Param& p, int64_t& stride) const {
-    const bool shared = first_ && gshared_;
+  const float* tap_w(const Param& p, bool shared, int64_t& stride) const {
     stride = shared ? 0 : p.n;
     return shared ? gshared_ + p.off : p.w;
   }
-  int conv_fwd(const ConvOp& c, const float* x, float* y, hipStream_t st, char* wsp = nullptr) {
+  int conv_fwd(const Step& S, const ConvOp& c, const float* x, float* y, hipStream_t st, char* wsp = nullptr) {
     const Param& p = ps_[c.p];
     if (p.tap) {
       int64_t wst;
-      const float* w = tap_w(p, wst);
+      const float* w = tap_w(p, S.wsh, wst);
       return flr_conv2d_fwd_t_ex(x, w, wst, y, K_, B_, c.Cin, c.H, c.H, c.Cout, c.k, c.k, c.stride, c.pad,
                                  wsp ? wsp : cws_, cws_n_, st);
     }
     return flr_conv2d_fwd(x, p.w, y, K_, B_, c.Cin, c.H, c.H, c.Cout, c.k, c.k, c.stride, c.pad, c.fws, c.fws_n, st);
   }
   // dx (when wanted) then dw, as ClientConv2d[T].backward
-  // With the weight-gradient stream (wgs_, wev_ < NEV), a tap-major conv's dW runs on
-  // it with the second workspace, forked here (dy ready on st), the data gradient
-  // on st.  The two write disjoint outputs; dy and x are not rewritten this step.
-  int conv_bwd(const ConvOp& c, const float* x, const float* dy, float* dx, hipStream_t st,
+  // With the weight-gradient stream (and two of its events left: this fork, and one
+  // kept for the join), a tap-major conv's dW runs on it with the second workspace,
+  // forked here (dy ready on st), the data gradient on st.  The two write disjoint
+  // outputs; dy and x are not rewritten this step.
+  int conv_bwd(Step& S, const ConvOp& c, const float* x, const float* dy, float* dx, hipStream_t st,
                const float* add = nullptr) {
     const Param& p = ps_[c.p];
     int rc;
     if (p.tap) {
       int64_t wst;
-      const float* w = tap_w(p, wst);
+      const float* w = tap_w(p, S.wsh, wst);
       hipStream_t ws = st;
       char* wsp = cws_;
-      if (wg_on_text_ && text_ && tev_ < TextStream::NEV - 1) {
-        if (hipEventRecord(text_->ev[tev_], st) != hipSuccess || hipStreamWaitEvent(text_->s, text_->ev[tev_], 0) != hipSuccess)
-          return launch_status("train_clients: text-stream weight-gradient fork");
-        ++tev_;
-        ws = text_->s;
+      if (S.wg_on_text && S.tx.left(2)) {  // TX_WG_JOIN stays free
+        FLR_TRY(ev_link(S.tx.take(), st, o_.text->s, "train_clients: text-stream weight-gradient fork"));
+        ws = o_.text->s;
         wsp = cws3_;
-      } else if (wgs_ && wev_ + 1 < WgradStream::NEV) {  // one event kept for the join
-        if (hipEventRecord(wgs_->ev[wev_], st) != hipSuccess || hipStreamWaitEvent(wgs_->s, wgs_->ev[wev_], 0) != hipSuccess)
-          return launch_status("train_clients: weight-gradient fork");
-        ++wev_;
-        ws = wgs_->s;
+      } else if (S.wg.left(2)) {
+        FLR_TRY(ev_link(S.wg.take(), st, o_.wgrad->s, "train_clients: weight-gradient fork"));
+        ws = o_.wgrad->s;
         wsp = cws2_;
       }
       if (dx && (rc = flr_conv2d_bwd_data_t_ex(dy, w, wst, add, dx, K_, B_, c.Cin, c.H, c.H, c.Cout, c.k, c.k,
@@ -1042,18 +1092,12 @@ class Net {
   int gtext_ = 0, ghead_ = 0;
   static constexpr int kEarlySlots = 32;  // clip_sumsq_blocks' partials per client (train_step.hip NBLK)
   int sq_early_base_ = -1;                // their first slot in sq_ (-1: none)
- public:
-  SideStream* side_ = nullptr;  // the optimizer's side stream (nullptr: the update runs on the caller's stream)
-  TextStream* text_ = nullptr;  // the text branch's stream (nullptr: the caller's stream)
-  WgradStream* wgs_ = nullptr;  // the weight-gradient stream (nullptr: on the caller's stream)
-  int wev_ = 0;                 // fork events used this step
-  bool stem_fused_ = false;     // bn1 + relu + maxpool fused (flr_batchnorm_relu_maxpool_fwd / _bwd)
- private:
-  bool pending_ = false;        // a side-stream update the next forward must wait for
+  Options o_;
+  const float* gshared_ = nullptr;  // the global vector the first step reads (Options::shared_first)
+  bool stem_fused_ = false;         // bn1 + relu + maxpool fused (flr_batchnorm_relu_maxpool_fwd / _bwd)
+  bool pending_ = false;            // a side-stream update the next forward must wait for
   char *sgd_ws_ = nullptr, *gws_ = nullptr, *rws_ = nullptr, *ews_ = nullptr, *cws_ = nullptr, *cws2_ = nullptr,
        *cws3_ = nullptr;
-  bool wg_on_text_ = false;  // this conv's dW on the text stream (the first FLR_WG_TEXT residual blocks)
-  int tev_ = 4;              // text-stream fork events used by them this step
   size_t sgd_ws_n_ = 0, gws_n_ = 0, rws_n_ = 0, ews_n_ = 0, cws_n_ = 0;
   float *ximg_ = nullptr, *y0_ = nullptr, *a0_ = nullptr, *d_a0_ = nullptr, *d_y0_ = nullptr, *p0_ = nullptr,
         *d_p0_ = nullptr, *d_x4_ = nullptr;
@@ -1063,6 +1107,8 @@ class Net {
         *dpre_ = nullptr, *dh_ = nullptr, *dh2_ = nullptr, *dh_direct_ = nullptr, *dgh_ = nullptr, *dgi_ = nullptr,
         *demb_ = nullptr;
 };
+
+#undef FLR_TRY
 
 }  // namespace tc
 }  // namespace flr
@@ -1113,30 +1159,32 @@ extern "C" int flr_train_clients_ex(const flr_resnet_gru_spec* spec, const float
   if (rc != FLR_OK) return rc;
   if (ld < net.P()) return FLR_ERR_ARG;
   float* step_loss = reinterpret_cast<float*>(base + align_up(net.bytes(), 256));
-  net.norms_ = norms_out;
+  // FLR_FUSED_RES and FLR_SHARED_FIRST are read once per process, at the first
+  // training call (the stream gates: per call)
   static const bool fuse_res = [] {
     const char* e = flr::knob("FLR_FUSED_RES");
     return !(e && e[0] == '0');
   }();
-  net.fuse_res_ = fuse_res;
   static const bool shared_first = [] {
     const char* e = flr::knob("FLR_SHARED_FIRST");
     return !(e && e[0] == '0');
   }();
-  net.shared_first_ = shared_first;
   const bool train_order = (flags & FLR_TC_TRAIN_ORDER) != 0;
   hipStream_t st = as_stream(stream);
-  net.side_ = side_stream(true, st);
-  net.text_ = text_stream(true, st);
-  net.wgs_ = wgrad_stream(true, st);
+  tc::Net::Options o;
+  o.norms = norms_out;
+  o.fuse_res = fuse_res;
+  o.shared_first = shared_first;
+  o.side = side_stream(true, st);
+  o.text = text_stream(true, st);
+  o.wgrad = wgrad_stream(true, st);
   if (train_order) {
-    net.xout_ = X;
-    net.xld_ = ld;
-    net.xneg_ = nneg;
-    rc = net.load_global_train(global, st);
-  } else {
-    rc = net.load_global(global, st);
+    o.xout = X;
+    o.xld = ld;
+    o.xneg = nneg;
   }
+  net.configure(o);
+  rc = train_order ? net.load_global_train(global, st) : net.load_global(global, st);
   if (rc != FLR_OK) return rc;
   const int64_t C0 = spec->in_channels, HW0 = spec->image_size * spec->image_size, T = spec->seq_len;
   for (int64_t s = 0; s < steps; ++s) {
@@ -1159,8 +1207,7 @@ extern "C" int64_t flr_resnet_gru_dead_ranges(const flr_resnet_gru_spec* spec, f
   if (!spec || cap < 0 || (cap > 0 && (!off || !n))) return -1;
   tc::Net net(*spec, 1, 1, weight_decay, 0.f, nullptr);
   if (net.layout() != FLR_OK) return -1;
-  std::vector<std::pair<int64_t, int64_t>> r;
-  net.dead_list(r);
+  const auto r = net.dead_list();
   for (int64_t i = 0; i < cap && i < (int64_t)r.size(); ++i) {
     off[i] = r[i].first;
     n[i] = r[i].second;

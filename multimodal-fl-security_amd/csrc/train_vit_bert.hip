@@ -93,6 +93,9 @@ struct LayerAct {
   float *mean1 = nullptr, *rstd1 = nullptr, *mean2 = nullptr, *rstd2 = nullptr;
 };
 
+#define FLR_TRY(x) \
+  if ((rc = (x)) != FLR_OK) return rc
+
 class Net {
  public:
   Net(const flr_vit_bert_spec& s, int64_t K, int64_t B, int64_t KC, int64_t steps, char* base)
@@ -286,14 +289,12 @@ class Net {
   }
 
   // the weight-gradient stream of the ViT layers' backward (nullptr: all on the caller's)
-  void set_wgrad_stream(WgradStream* w) { wgs_ = w; }
+  void set_wgrad_stream(AuxStream* w) { wgs_ = w; }
 
  private:
   // ---- the forward + backward of one pass ----------------------------------
   int pass(const float* images, const int64_t* tokens, const int64_t* labels, const float* mask, float* loss_row) {
     int rc;
-#define FLR_TRY(x) \
-  if ((rc = (x)) != FLR_OK) return rc
     const auto& s = s_;
     const int64_t kc = kc_, Rv = B_ * Tv_, Rb = B_ * Tb_, Dv = Dv_, Db = Db_, BNP = B_ * NP_;
     // ================= forward =================
@@ -384,17 +385,15 @@ class Net {
     // With the weight-gradient stream, layer i's weight / bias gradients run on it (as the
     // ViT layers' below): what they read (d(f), dpre, d(attn), dqkv) alternates between two
     // copies, rewritten two layers later after the caller's stream waited on that layer.
-    wev_ = 0;
-    side_ = wgs_ != nullptr && !dry_ && vl_.size() <= 64 && bl_.size() <= 64 &&
-            5 * (vl_.size() + bl_.size()) <= (size_t)WgradStream::NEV;
-    hipEvent_t bdone[64];
+    wev_ = {wgs_, 0};
+    side_ = side_eligible();
+    DoneRing bdone;
     int bit = 0;
     for (int i = (int)bl_.size() - 1; i >= 0; --i, ++bit) {
       const Layer& L = bl_[i];
       LayerAct& a = ba_[i];
       const float* xin = i > 0 ? ba_[i - 1].y2 : xe_;
-      if (use_side() && bit >= 2 && hipStreamWaitEvent(st_, bdone[(bit - 2) & 63], 0) != hipSuccess)
-        return launch_status("train_vit_bert: weight-gradient join");
+      if (use_side()) FLR_TRY(bdone.wait_behind(bit, st_));
       const bool odd = use_side() && (bit & 1);
       float* by2 = odd ? bdy2b_ : bdy2;
       float* bp = odd ? bdp2_ : bdp_;
@@ -404,22 +403,19 @@ class Net {
       FLR_TRY(mlp_bwd(by2, Rb, Db, Fb_, L, a.y1, a.pre, a.hm, bp, bdm));
       FLR_TRY(launch(add_kernel, kc * Rb * Db, by2, bdm, bdsum, kc * Rb * Db));  // y1 feeds LN2 and the MLP
       FLR_TRY(ln_bwd(bdsum, a.s1, L.ln1w, L.ln1b, a.mean1, a.rstd1, nullptr, b1, Rb, Db));  // d(x) and d(attn)
-      if (use_side()) FLR_TRY(link(st_, wgs_->s));
+      if (use_side()) FLR_TRY(link());
       FLR_TRY(dinput(b1, Rb, L.projw, Db, bdc));
       FLR_TRY(dweight(b1, Rb * Db, Db, Rb, a.ctx, Rb * Db, Db, G(L.projw), Db, Db));
       FLR_TRY(rowsum(b1, Rb * Db, Db, Rb, Db, G(L.projb)));
       if (!dry_) FLR_TRY(flr_attention_bwd(a.qkv, a.ctx, bdc, a.lse, kc * B_, Tb_, s.bert_heads, 64, bq, st_));
-      if (use_side()) FLR_TRY(link(st_, wgs_->s));
+      if (use_side()) FLR_TRY(link());
       FLR_TRY(dinput(bq, Rb, L.qkvw, Db, bdm));
       FLR_TRY(dweight(bq, Rb * 3 * Db, 3 * Db, Rb, xin, Rb * Db, Db, G(L.qkvw), Db, Db));
       FLR_TRY(rowsum(bq, Rb * 3 * Db, 3 * Db, Rb, 3 * Db, G(L.qkvb)));
-      if (use_side()) FLR_TRY(mark(&bdone[bit & 63]));
+      if (use_side()) FLR_TRY(bdone.mark(bit, wev_, wgs_->s));
       FLR_TRY(launch(add_kernel, kc * Rb * Db, b1, bdm, bdx, kc * Rb * Db));  // x feeds LN1 and qkv
     }
-    if (use_side())
-      for (int j = std::max(0, bit - 2); j < bit; ++j)
-        if (hipStreamWaitEvent(st_, bdone[j & 63], 0) != hipSuccess)
-          return launch_status("train_vit_bert: weight-gradient join");
+    if (use_side()) FLR_TRY(bdone.drain(bit, st_));
     side_ = false;
     FLR_TRY(ln_bwd(bdx, e_, p_ew_, p_eb_, meane_, rstde_, nullptr, bdm, Rb, Db));
     if (!dry_) {
@@ -445,16 +441,14 @@ class Net {
     // of three, d(attn), dqkv, the MLP's dpre in two copies) is rewritten only two layers
     // later, after the caller's stream waited on that layer's side events.
     // (wev_ continues from the BERT layers: one event set per pass)
-    side_ = wgs_ != nullptr && !dry_ && vl_.size() <= 64 && bl_.size() <= 64 &&
-            5 * (vl_.size() + bl_.size()) <= (size_t)WgradStream::NEV;
+    side_ = side_eligible();
     float* ring[3] = {vdA, vdB, vdr3_};
-    hipEvent_t done[64];
+    DoneRing done;
     int it = 0;
     for (int i = (int)vl_.size() - 1; i >= 0; --i, ++it) {
       const Layer& L = vl_[i];
       LayerAct& a = va_[i];
-      if (use_side() && it >= 2 && hipStreamWaitEvent(st_, done[(it - 2) & 63], 0) != hipSuccess)
-        return launch_status("train_vit_bert: weight-gradient join");
+      if (use_side()) FLR_TRY(done.wait_behind(it, st_));
       vdA = use_side() ? ring[it % 3] : vdA;
       vdB = use_side() ? ring[(it + 1) % 3] : vdB;
       float* vx2 = use_side() && (it & 1) ? vdx2b_ : vdx2;
@@ -463,16 +457,16 @@ class Net {
       // vdA = dL/d(s2_i) = dL/d(r_i): the next LayerNorm's dx
       FLR_TRY(mlp_bwd(vdA, Rv, Dv, Mv_, L, a.y2, a.pre, a.hm, vp, vdm));  // vdm = d(y2)
       FLR_TRY(ln_bwd(vdm, a.s2, L.ln2w, L.ln2b, a.mean2, a.rstd2, vdA, vx2, Rv, Dv));  // d(s_in) and d(attn)
-      if (use_side()) FLR_TRY(link(st_, wgs_->s));
+      if (use_side()) FLR_TRY(link());
       FLR_TRY(dinput(vx2, Rv, L.projw, Dv, vdc));
       FLR_TRY(dweight(vx2, Rv * Dv, Dv, Rv, a.ctx, Rv * Dv, Dv, G(L.projw), Dv, Dv));
       FLR_TRY(rowsum(vx2, Rv * Dv, Dv, Rv, Dv, G(L.projb)));
       if (!dry_) FLR_TRY(flr_attention_bwd(a.qkv, a.ctx, vdc, a.lse, kc * B_, Tv_, s.vit_heads, 64, vq, st_));
-      if (use_side()) FLR_TRY(link(st_, wgs_->s));
+      if (use_side()) FLR_TRY(link());
       FLR_TRY(dinput(vq, Rv, L.qkvw, Dv, vdh));
       FLR_TRY(dweight(vq, Rv * 3 * Dv, 3 * Dv, Rv, a.h, Rv * Dv, Dv, G(L.qkvw), Dv, Dv));
       FLR_TRY(rowsum(vq, Rv * 3 * Dv, 3 * Dv, Rv, 3 * Dv, G(L.qkvb)));
-      if (use_side()) FLR_TRY(mark(&done[it & 63]));
+      if (use_side()) FLR_TRY(done.mark(it, wev_, wgs_->s));
       if (i > 0) {
         // LN1 with the residual: ds = vdx2 (s1 feeds LN2 only); dx -> d(s2_{i-1}) = d(r_{i-1})
         FLR_TRY(ln_bwd(vdh, a.s1, L.ln1w, L.ln1b, a.mean1, a.rstd1, vx2, vdB, Rv, Dv));
@@ -481,16 +475,12 @@ class Net {
         // block 0: x0 feeds LN1 (no residual) and LN2 (as x): the two paths summed (into
         // vdA, which this layer's side work reads: joined first)
         FLR_TRY(ln_bwd(vdh, x0_, L.ln1w, L.ln1b, a.mean1, a.rstd1, nullptr, vdB, Rv, Dv));
-        if (use_side() && hipStreamWaitEvent(st_, done[it & 63], 0) != hipSuccess)
-          return launch_status("train_vit_bert: weight-gradient join");
+        if (use_side()) FLR_TRY(done.wait(it, st_));
         FLR_TRY(launch(add_kernel, kc * Rv * Dv, vdB, vx2, vdA, kc * Rv * Dv));
       }
     }
     // every side event of the layers joined (the last two were not waited on yet)
-    if (use_side())
-      for (int j = std::max(0, it - 2); j < it; ++j)
-        if (hipStreamWaitEvent(st_, done[j & 63], 0) != hipSuccess)
-          return launch_status("train_vit_bert: weight-gradient join");
+    if (use_side()) FLR_TRY(done.drain(it, st_));
     side_ = false;
     // ClientViTTokens.backward: dpos / dcls = sums over the batch rows, dtok = the patch rows
     if (!dry_) {
@@ -501,7 +491,6 @@ class Net {
     // patch embedding (ClientLinear.backward; the patches need no gradient)
     FLR_TRY(dweight(dtok_, BNP * Dv, Dv, BNP, patches_, BNP * Cpp_, Cpp_, G(p_pew_), Cpp_, Cpp_));
     FLR_TRY(rowsum(dtok_, BNP * Dv, Dv, BNP, Dv, G(p_peb_)));
-#undef FLR_TRY
     return FLR_OK;
   }
 
@@ -509,15 +498,14 @@ class Net {
   int mlp_bwd(const float* dy, int64_t M, int64_t D, int64_t Fh, const Layer& L, const float* x, const float* pre,
               const float* hm, float* dpre, float* dx) {
     int rc;
-    if (use_side() && (rc = link(st_, wgs_->s)) != FLR_OK) return rc;  // dy ready
-    if ((rc = gemm(dy, M * D, D, 1, W(L.fc2w), D * Fh, 1, Fh, dpre, M * Fh, Fh, 1, nullptr, 0, nullptr,
-                   FLR_ACT_DGELU, nullptr, pre, nullptr, M, Fh, D)) != FLR_OK)
-      return rc;
-    if ((rc = dweight(dy, M * D, D, M, hm, M * Fh, Fh, G(L.fc2w), Fh, Fh)) != FLR_OK) return rc;
-    if ((rc = rowsum(dy, M * D, D, M, D, G(L.fc2b))) != FLR_OK) return rc;
-    if (use_side() && (rc = link(st_, wgs_->s)) != FLR_OK) return rc;  // dpre ready
-    if ((rc = dinput(dpre, M, L.fc1w, D, dx)) != FLR_OK) return rc;
-    if ((rc = dweight(dpre, M * Fh, Fh, M, x, M * D, D, G(L.fc1w), D, D)) != FLR_OK) return rc;
+    if (use_side()) FLR_TRY(link());  // dy ready
+    FLR_TRY(gemm(dy, M * D, D, 1, W(L.fc2w), D * Fh, 1, Fh, dpre, M * Fh, Fh, 1, nullptr, 0, nullptr, FLR_ACT_DGELU,
+                 nullptr, pre, nullptr, M, Fh, D));
+    FLR_TRY(dweight(dy, M * D, D, M, hm, M * Fh, Fh, G(L.fc2w), Fh, Fh));
+    FLR_TRY(rowsum(dy, M * D, D, M, D, G(L.fc2b)));
+    if (use_side()) FLR_TRY(link());  // dpre ready
+    FLR_TRY(dinput(dpre, M, L.fc1w, D, dx));
+    FLR_TRY(dweight(dpre, M * Fh, Fh, M, x, M * D, D, G(L.fc1w), D, D));
     return rowsum(dpre, M * Fh, Fh, M, Fh, G(L.fc1b));
   }
 
@@ -562,19 +550,39 @@ class Net {
     return flr_bgemm_ex(A, ak, am, ar, Bm, bk, bn, br, C, ck, cm, cn, nullptr, 0, nullptr, FLR_ACT_NONE, nullptr,
                         nullptr, nullptr, kc_, M, N, R, gws2_, gws_n_, wgs_->s);
   }
-  // event e recorded on `from`; `to` waits on it
-  int link(hipStream_t from, hipStream_t to) {
-    if (wev_ >= WgradStream::NEV) return FLR_ERR_UNSUPPORTED;
-    hipEvent_t e = wgs_->ev[wev_++];
-    if (hipEventRecord(e, from) != hipSuccess || hipStreamWaitEvent(to, e, 0) != hipSuccess)
-      return launch_status("train_vit_bert: weight-gradient stream event");
-    return FLR_OK;
+  // the caller's stream's work so far, ready for the weight-gradient stream
+  // (the next event recorded on st_, the stream waits on it)
+  int link() {
+    if (!wev_.left(1)) return FLR_ERR_UNSUPPORTED;
+    return ev_link(wev_.take(), st_, wgs_->s, "train_vit_bert: weight-gradient stream event");
   }
-  // the layer's side work so far, as an event the caller waits on later
-  int mark(hipEvent_t* out) {
-    if (wev_ >= WgradStream::NEV) return FLR_ERR_UNSUPPORTED;
-    *out = wgs_->ev[wev_++];
-    return hipEventRecord(*out, wgs_->s) == hipSuccess ? FLR_OK : launch_status("train_vit_bert: side mark");
+  // A layer loop's side work, joined two iterations behind: what iteration `it`
+  // left on the weight-gradient stream is marked by an event, and the caller's
+  // stream waits on it before iteration it + 2 rewrites the scratch it reads.
+  // Two marks are outstanding at most.
+  struct DoneRing {
+    hipEvent_t ev[2] = {};
+    int wait(int it, hipStream_t st) const {
+      return ev_wait(st, ev[it & 1], "train_vit_bert: weight-gradient join");
+    }
+    int wait_behind(int it, hipStream_t st) const { return it >= 2 ? wait(it - 2, st) : FLR_OK; }
+    int mark(int it, EventCursor& c, hipStream_t side) {
+      if (!c.left(1)) return FLR_ERR_UNSUPPORTED;
+      ev[it & 1] = c.take();
+      return ev_record(ev[it & 1], side, "train_vit_bert: side mark");
+    }
+    // after n iterations: the last two marks, not waited on yet
+    int drain(int n, hipStream_t st) const {
+      for (int j = std::max(0, n - 2); j < n; ++j)
+        if (int rc = wait(j, st)) return rc;
+      return FLR_OK;
+    }
+  };
+  // the layers' weight / bias gradients may go to the weight-gradient stream: five
+  // events per layer (four links and the mark), one event set per pass
+  bool side_eligible() const {
+    return wgs_ != nullptr && !dry_ && vl_.size() <= 64 && bl_.size() <= 64 &&
+           5 * (vl_.size() + bl_.size()) <= (size_t)wgs_->nev;
   }
   bool use_side() const { return side_ && wgs_ && !dry_; }
   int rowsum(const float* X, int64_t xk, int64_t xm, int64_t M, int64_t N, float* out) {
@@ -673,13 +681,15 @@ class Net {
   float *vdq_ = nullptr, *vdp_ = nullptr, *dtok_ = nullptr;
   float *vdq2_ = nullptr, *vdp2_ = nullptr, *vdx2b_ = nullptr, *vdr3_ = nullptr;
   char *gws2_ = nullptr, *rws2_ = nullptr;
-  WgradStream* wgs_ = nullptr;  // the weight-gradient stream (nullptr: everything on st_)
+  AuxStream* wgs_ = nullptr;    // the weight-gradient stream (nullptr: everything on st_)
   bool side_ = false;           // route dweight / rowsum to it (set around the ViT layers)
-  int wev_ = 0;                 // events used this pass
+  EventCursor wev_;             // its next free event this pass
   float* bd_[6] = {};
   float *bdq_ = nullptr, *bdp_ = nullptr;
   float *bdq2_ = nullptr, *bdp2_ = nullptr, *bdy2b_ = nullptr, *bd1b_ = nullptr;
 };
+
+#undef FLR_TRY
 
 inline int64_t auto_chunk(int64_t K, int64_t chunk) { return chunk > 0 ? std::min(chunk, K) : std::min<int64_t>(K, 32); }
 

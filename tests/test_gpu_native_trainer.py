@@ -50,6 +50,36 @@ def test_native_trainer_bit_identical_to_python_trainer(cuda, spec_name, B, nneg
     assert torch.equal(X, X_py), (X - X_py).abs().max()
 
 
+@pytest.fixture(scope="module")
+def c3_default_streams(cuda):
+    """flr_train_clients on the full ResNet-18 + GRU model (tap-major convs, the
+    three downsample blocks, the two blocks whose weight gradients go to the text
+    stream) with every auxiliary stream at its default: the inputs and the result."""
+    spec, K, B, steps = ModelSpec(), 3, 8, 2
+    cfg = TrainConfig(local_steps=steps)
+    glob = initial_global(spec, 42, cuda)
+    batches = synthetic_batches(spec, steps, range(K), B, cuda)
+    masks = make_dropout_masks(spec, steps, K, B, cuda, seed=11)
+    X, loss, norms = nt.train_clients(spec, glob, batches, cfg, masks, negate_rows=1)
+    torch.cuda.synchronize()
+    return (spec, glob, batches, cfg, masks), (X, loss, norms)
+
+
+# where the work runs changes no bit: the text branch, the weight gradients and the
+# shortcut convs on the caller's stream instead of their own (the gates are read per call)
+@pytest.mark.parametrize("off", [("FLR_TEXT_STREAM",), ("FLR_WGRAD_STREAM",), ("FLR_TEXT_STREAM", "FLR_WGRAD_STREAM"),
+                                 ("FLR_WG_TEXT",)], ids="+".join)
+def test_native_trainer_same_bits_on_any_stream(c3_default_streams, knob, off):
+    (spec, glob, batches, cfg, masks), (X0, loss0, norms0) = c3_default_streams
+    for name in off:
+        knob(name, "0")
+    X, loss, norms = nt.train_clients(spec, glob, batches, cfg, masks, negate_rows=1)
+    torch.cuda.synchronize()
+    assert torch.equal(X, X0), (X - X0).abs().max()
+    assert torch.equal(loss, loss0), (loss, loss0)
+    assert torch.equal(norms, norms0), (norms, norms0)
+
+
 def _gpu_relu_inputs(spec, w, images, tokens, mask, cuda):
     """The ReLU inputs of one train-mode forward of the engine's kernels (the
     Python trainer's composition, bit-identical to flr_train_clients:
@@ -185,6 +215,30 @@ def test_native_vit_bert_bit_identical_to_python_trainer(cuda, spec_name, K, B, 
     assert torch.equal(loss, loss_py), (loss, loss_py)
     assert torch.equal(tr.norms, norms_py), (tr.norms, norms_py)
     assert torch.equal(X, X_py), (X - X_py).abs().max()
+
+
+def test_native_vit_bert_same_bits_without_wgrad_stream(cuda, knob):
+    """The vit_tiny case with the layers' weight / bias gradients on the caller's
+    stream (FLR_WGRAD_STREAM=0, read per call) and on their own: the same bits."""
+    from flr.models.multimodal import VIT_BERT_TINY
+    spec = VIT_BERT_TINY.__class__(**{**VIT_BERT_TINY.__dict__, "dropout": 0.5})
+    K, B, steps, chunk, nneg = 3, 4, 2, 2, 1
+    glob = initial_global(spec, 42, cuda)
+    batches = synthetic_batches(spec, steps, range(K), B, cuda)
+    masks = make_dropout_masks(spec, steps, K, B, cuda, seed=5)
+    got = []
+    for value in ("0", None):
+        knob("FLR_WGRAD_STREAM", value)
+        tr = nt.NativeRoundTrainer(spec, K, cuda, TrainConfig(local_steps=steps, client_chunk=chunk), batch=B)
+        tr.load_global(glob)
+        loss = tr.local_update(batches, masks, negate_rows=nneg).clone()
+        torch.cuda.synchronize()
+        got.append((tr.X.data[:, : tr.P].clone(), loss, tr.norms.clone()))
+    (X0, loss0, norms0), (X1, loss1, norms1) = got
+    assert torch.isfinite(X1).all()
+    assert torch.equal(X0, X1), (X0 - X1).abs().max()
+    assert torch.equal(loss0, loss1), (loss0, loss1)
+    assert torch.equal(norms0, norms1), (norms0, norms1)
 
 
 def test_native_vit_bert_matches_reference_loop(cuda):

@@ -1,5 +1,6 @@
-"""Diagnostic: node count of a round's captured training-phase HIP graph
-(RoundEngine._capture) for a BASELINE config preset and client count.
+"""Diagnostic: node counts by type and the edge count of a round's captured
+training-phase HIP graph (RoundEngine._capture) for a BASELINE config preset
+and client count, then one replay.  The topology does not depend on K.
 Usage: python tools/graph_nodes.py C4 256"""
 import ctypes
 import os
@@ -35,8 +36,13 @@ def main():
         t = ctypes.c_int(-1)
         hip.hipGraphNodeGetType(ctypes.c_void_p(nodes[i]), ctypes.byref(t))
         kinds[t.value] = kinds.get(t.value, 0) + 1
+    # the dependency edges: with the node counts, the graph's topology (every fork
+    # and join between the trainers' streams is one or more of them)
+    e = ctypes.c_size_t(0)
+    st3 = hip.hipGraphGetEdges(ctypes.c_void_p(eng._graph.raw_cuda_graph()), None, None, ctypes.byref(e))
     # hipGraphNodeType: 0 kernel, 1 memcpy, 2 memset, 3 host, 4 graph, 5 empty, 6 wait event, 7 event record
-    print(f"{cfg} K={K}: graph nodes {n.value} (status {st}/{st2}) by type {kinds}", flush=True)
+    print(f"{cfg} K={K}: graph nodes {n.value} edges {e.value} (status {st}/{st2}/{st3}) by type "
+          f"{dict(sorted(kinds.items()))}", flush=True)
     eng._graph.instantiate()
     eng.run_round()
     torch.cuda.synchronize()
