@@ -826,6 +826,104 @@ int flr_rows_combine_from(const float* X, int64_t K, int64_t P, int64_t ldx,
                           const float* center, const float* beta /* device [K] */,
                           float* out, void* stream);
 
+/* ---- FLAME (Nguyen et al., USENIX Security 2022) ---------------------------
+ * "FLAME: Taming Backdoors in Federated Learning", Algorithm 1: the backdoor
+ * defense.  No reference counterpart.  The clients are clustered by the cosine
+ * distances of their updates, the majority cluster is admitted, the admitted
+ * updates are clipped to the median update norm and averaged, and Gaussian noise
+ * scaled by that median is added.  It needs no attacker count and no server
+ * data.  Four calls: flr_rows_gram (above), flr_flame_select, flr_rows_combine_from
+ * (above) and flr_add_gaussian, each enqueued on the stream with no host
+ * synchronisation; nothing is written on an error.
+ *
+ * flr_flame_select: one launch of one workgroup, a lane per client.  With G the
+ * Gram matrix of the updates u_i = x_i - g (flr_rows_gram with center g; with no
+ * center the paper's Algorithm 1 read literally, the cosines of the models), all
+ * arithmetic fp64, every operation rounded on its own, only + - * / sqrt:
+ *   1. distances.  n_i = sqrt(G_ii).  Row i is bad when G_ii is not finite: it has
+ *      no edges, is never admitted, and sets bit 1 of flags.  For i != j, both
+ *      good:  d_ij = 1 when n_i == 0 or n_j == 0, else
+ *        d_ij = 1 - G_ij / (n_i * n_j)     (the product, the quotient, the
+ *                                           subtraction; not clamped)
+ *      A NaN d_ij is no edge.  G is taken as symmetric (flr_rows_gram's is, bit
+ *      for bit): the kernel reads G_ji for d_ij.
+ *   2. clustering.  The paper calls HDBSCAN with min_cluster_size = m = K/2 + 1
+ *      (integer division), min_samples = 1, allow_single_cluster = True on these
+ *      distances.  Two facts give that call a closed form:
+ *        - the core distance of a point (min_samples = 1: the distance to its
+ *          nearest neighbour) is at most its distance to anyone, so the mutual
+ *          reachability distance max(core_i, core_j, d_ij) is d_ij itself;
+ *        - with 2 m > K two clusters of m points cannot coexist, so the
+ *          condensed tree never splits: the one selected cluster is the first
+ *          single-linkage component that reaches m points.
+ *      So: t* = the smallest t for which the graph on the good rows with the
+ *      edges {d_ij <= t} has a connected component of at least m rows; that
+ *      component is admitted (it is unique: two would hold more than K rows),
+ *      every other row is rejected.  Edges of equal weight enter together, so no
+ *      tie-breaking order exists that could change the result.  The kernel runs
+ *      Prim's minimum spanning tree over the implicit distance matrix (lane j
+ *      keeps its key, each step reads one row of G coalesced and ends in a
+ *      workgroup arg-min), sorts the K - 1 tree edges in LDS and merges them level
+ *      by level until a component holds m rows: the components of any minimum
+ *      spanning tree cut at t are those of the threshold graph, so ties in
+ *      Prim's choice cannot change the answer either.
+ *      Because the cluster is cut the moment it reaches m, the rule typically
+ *      admits m or m + 1 clients, about half: that is the published rule, and m
+ *      is the knob.
+ *   3. fewer than m good rows, or no component of m rows (NaN distances): no
+ *      cluster.  keep is all 0, every beta 0, sigma 0, t* = +inf, L = 0, bit 0 of
+ *      flags; flr_rows_combine_from then returns the center bit for bit.
+ *      m == 1 (only K == 1 allows it): the good row is admitted, t* = 0.
+ *   4. clipping bound.  e_i = norms[i] when norms is given (the caller's update
+ *      norms when G was taken without a center: flr_row_norms about g), else
+ *      n_i.  S = the lower median of the K values e, sort(e)[(K-1)/2] with NaN
+ *      sorted last (flr_centered_clip's convention), over all clients, rejected
+ *      ones included, as in the paper.  L = the admitted count.
+ *        gamma_i = S / e_i when e_i > S, else 1
+ *        beta_i  = (float)(gamma_i / L) for an admitted row, exactly 0.f for a
+ *                  rejected one
+ *        sigma   = (float)(lambda * S); 0.f with no cluster
+ * Given the same G bits a numpy restatement of steps 1-4 therefore gives the
+ * same keep, t*, S, L, beta, sigma and flags bit for bit (sqrt and the four
+ * operations are correctly rounded on the device; the library is built with
+ * -ffp-contract=off): tests/flame_ref.py is that restatement.
+ * G: device fp64 [K][K]; norms: optional device fp64 [K]; keep: device int32
+ * [K], 1 admitted, 0 rejected; beta: device fp32 [K]; sigma: device fp32 [1];
+ * optional (NULL: not written) stats fp64 [3]: S, t*, L; flags int32 [1].
+ * Bytes: G read once (one row per step; 8 MB at K = 1024, from L2).  About K
+ * dependent steps: latency-bound.
+ * FLR_ERR_ARG: null G, keep, beta or sigma; K < 1; m > K or 2 m <= K; lambda
+ * negative, NaN or infinite.  FLR_ERR_UNSUPPORTED: K > 1024 (flr_rows_gram's
+ * limit; one lane per client). */
+int flr_flame_select(const double* G, const double* norms /* optional */, int64_t K, int64_t m,
+                     double lambda, int32_t* keep, float* beta, float* sigma /* device [1] */,
+                     double* stats /* optional: S, t*, L */, int32_t* flags /* optional */,
+                     void* stream);
+/* flr_add_gaussian: v_k <- fl(v_k + fl(sigma * z_k)) in place, k = 0 .. P-1, two
+ * separately rounded fp32 operations; z standard normal.  sigma: device fp32 [1]
+ * (flr_flame_select's); sigma == 0 leaves every bit of v as it is (-0.f
+ * included).  The four consecutive global coordinate indices 4c .. 4c+3,
+ * c = (col0 + k) >> 2, share one Philox4x32-10 block (the round is written out
+ * at flr_fang_trim_rows) with key (seed & 0xffffffff, seed >> 32) and counter
+ * (c & 0xffffffff, c >> 32, 0, draw_stream).  With its words w0..w3, fp32:
+ *   u1 = ((w0 >> 8) + 1) * 2^-24  in (0, 1];   u2 = (w1 >> 8) * 2^-24  in [0, 1)
+ *   r  = sqrtf(fl(-2 * logf(u1)));  a = fl(6.2831853071795864769f * u2)
+ *   z0 = fl(r * cosf(a));  z1 = fl(r * sinf(a))
+ * z2 and z3 come from (w2, w3) in the same way; index 4c + j takes z_j.  logf,
+ * sinf and cosf are the accurate library functions, not the fast intrinsics
+ * (within 1e-5 absolute of the fp64 evaluation; |z| <= sqrt(48 ln 2) < 5.78).
+ * col0 >= 0: the global index of v[0], so a column range called with its own
+ * col0 gives that range of the whole call bit for bit.  A lane owns one Philox
+ * block: the lanes at the two ends compute a whole block and use the part of it
+ * inside [0, P).  The block's four floats move in one 16-byte access when their
+ * address is 16-byte aligned ((address of v) / 4 - col0 a multiple of 4), else
+ * in four 4-byte accesses: the same bits.  Bytes moved: 8 * P.
+ * FLR_ERR_ARG: null v or sigma; P < 0; col0 < 0 or col0 + P past 2^63 - 1.
+ * FLR_ERR_UNSUPPORTED: more than 2^31 - 1 workgroups of 256 blocks (P beyond
+ * 2^41).  P == 0: FLR_OK, nothing enqueued. */
+int flr_add_gaussian(float* v, int64_t P, const float* sigma /* device [1] */, uint64_t seed,
+                     uint32_t draw_stream, int64_t col0, void* stream);
+
 /* ---- the robust learning rate, RLR (Ozdayi, Kantarcioglu, Gel, AAAI 2021) ----
  * "Defending against Backdoors in Federated Learning with Robust Learning Rate":
  * per coordinate the clients vote with the sign of their update against the

@@ -26,11 +26,12 @@
 //   flr_fang_trim_rows   per coordinate the attackers sit beyond the benign
 //                        extreme on the side opposite s, at points drawn with a
 //                        counter-based generator (Philox4x32-10, written out
-//                        here: no RNG library) keyed by the coordinate's global
+//                        in philox.h: no RNG library) keyed by the coordinate's global
 //                        index, so a column range gives the whole call's bits.
 //                        One pass: a lane owns a float4 of coordinates, walks the
 //                        benign rows with 16 loads in flight and writes the f
 //                        rows.  (nb + f) * P * 4 bytes.
+#include "philox.h"
 #include "rows_pass.h"
 
 namespace flr {
@@ -314,25 +315,7 @@ int strength(const double* G, const double* b, const double* c, int64_t K, int64
 
 // ---- the trimmed-mean attack ----
 
-// Word 0 of Philox4x32-10 (flr.h writes the round out).
-__device__ __forceinline__ uint32_t philox_word0(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
-                                                 uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    if (r > 0) {
-      k0 += 0x9E3779B9u;
-      k1 += 0xBB67AE85u;
-    }
-    const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-    const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-    c1 = (uint32_t)p1;
-    c3 = (uint32_t)p0;
-    c0 = n0;
-    c2 = n2;
-  }
-  return c0;
-}
-
+// The draws: word 0 of Philox4x32-10 (philox.h).
 template <bool VEC>
 __global__ __launch_bounds__(THREADS) void trim_kernel(float* __restrict__ X, int64_t nb, int64_t P, int64_t ldx,
                                                        int64_t nmal, const float* __restrict__ g, float bscale,

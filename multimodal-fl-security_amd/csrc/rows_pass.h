@@ -1,5 +1,5 @@
 // The column pass over a client matrix, shared by the aggregation and attack
-// units (agg_mean, agg_norm, agg_cclip, agg_dnc, agg_foolsgold, agg_rlr,
+// units (agg_mean, agg_norm, agg_cclip, agg_dnc, agg_flame, agg_foolsgold, agg_rlr,
 // attack_colluding, attack_fang, attack_minmax, attack_replace): a lane owns one float4 of
 // coordinates, or one coordinate, and walks the rows.  What is here has at least
 // two users and takes no flag that says which caller it serves; a unit whose loop

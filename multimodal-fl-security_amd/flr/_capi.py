@@ -106,6 +106,9 @@ SIGNATURES = {
     "flr_foolsgold_weights": (_int, [_c_void_p, _i64, ctypes.c_double, _c_void_p, _c_void_p, _c_void_p, _c_void_p,
                                      _c_void_p]),
     "flr_rows_combine_from": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "flr_flame_select": (_int, [_c_void_p, _c_void_p, _i64, _i64, ctypes.c_double, _c_void_p, _c_void_p, _c_void_p,
+                                _c_void_p, _c_void_p, _c_void_p]),
+    "flr_add_gaussian": (_int, [_c_void_p, _i64, _c_void_p, ctypes.c_uint64, ctypes.c_uint32, _i64, _c_void_p]),
     "flr_sign_vote": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _c_void_p]),
     "flr_rlr_apply": (_int, [_c_void_p, _c_void_p, _c_void_p, _i64, _i64, ctypes.c_float, _c_void_p, _c_void_p,
                              _c_void_p]),

