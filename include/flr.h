@@ -1172,6 +1172,47 @@ int flr_conv2d_bwd_data_t_ex(const float* dy, const float* w_t, int64_t w_stride
                              int64_t H, int64_t W, int64_t Cout, int64_t KH, int64_t KW,
                              int64_t stride, int64_t pad, void* workspace,
                              size_t workspace_bytes, void* stream);
+/* flr_conv2d_bwd_data_t_ex with the residual block's strided 1x1 shortcut folded
+ * in: dx = dgrad(conv) [+ add], then dx += dgrad(shortcut) where the shortcut is
+ * the 1x1 convolution of the same K, B, Cin, H, W and stride, pad 0, Cout_ds
+ * output channels, gradient dy_ds [K][Cout_ds][B][Ho][Wo] and tap-major weights
+ * w_ds (w_ds_stride floats between clients, 0: one shared copy).  The values are
+ * those of the two calls flr_conv2d_bwd_data_t_ex(conv, add, dx) then
+ * flr_conv2d_bwd_data_t_ex(shortcut, add = dx, dx), bit for bit.  dy_ds and w_ds
+ * NULL: no shortcut (flr_conv2d_bwd_data_t_ex itself).
+ *
+ * Stride 2 with H and W even may run as ONE launch (the fused form): a workgroup
+ * walks the four stride-parity classes of its pixels (and the shortcut) with the
+ * per-class kernel's K-loop, sums each class's split-K ranges in the reduce pass's
+ * order without writing partials, and stores whole rows of dx.  The knob
+ * FLR_DGRAD_FUSED (flr_set_knob, read per launch) chooses: 0 the per-class
+ * launches, 1 the fused form wherever supported, unset the per-shape preference
+ * (flr_conv2d_dgrad_fused_preferred).  Either form writes the same bits; every
+ * other geometry, a dx that is not 8-byte aligned, and an in-place call
+ * (add == dx) with a class no tap reaches take the per-class launches. */
+int flr_conv2d_bwd_data_t_sc(const float* dy, const float* w_t, int64_t w_stride,
+                             const float* add, float* dx, int64_t K, int64_t B, int64_t Cin,
+                             int64_t H, int64_t W, int64_t Cout, int64_t KH, int64_t KW,
+                             int64_t stride, int64_t pad, const float* dy_ds,
+                             const float* w_ds, int64_t w_ds_stride, int64_t Cout_ds,
+                             void* workspace, size_t workspace_bytes, void* stream);
+/* 1 when the geometry has a fused form (tap-major, stride 2, H and W even). */
+int flr_conv2d_dgrad_fused_supported(int64_t K, int64_t B, int64_t Cin, int64_t H, int64_t W,
+                                     int64_t Cout, int64_t KH, int64_t KW, int64_t stride,
+                                     int64_t pad);
+/* 1 when a call of this geometry (shortcut != 0: with a folded shortcut) runs
+ * fused under the current FLR_DGRAD_FUSED setting: supported, and the knob is 1
+ * or unset with the shape among those measured faster fused on MI355X. */
+int flr_conv2d_dgrad_fused_preferred(int64_t K, int64_t B, int64_t Cin, int64_t H, int64_t W,
+                                     int64_t Cout, int64_t KH, int64_t KW, int64_t stride,
+                                     int64_t pad, int shortcut);
+/* The split-K count of stride-parity class cls_index (row-major over (ih % stride,
+ * iw % stride)) of the data gradient given a workspace of workspace_bytes: the
+ * per-class launch's count, which the fused form reproduces in-register.
+ * 0: no such class. */
+int flr_conv2d_dgrad_class_splits(int64_t K, int64_t B, int64_t Cin, int64_t H, int64_t W,
+                                  int64_t Cout, int64_t KH, int64_t KW, int64_t stride,
+                                  int64_t pad, int cls_index, size_t workspace_bytes);
 /* 1 when flr_conv2d_fwd_t_ex (dgrad == 0) or flr_conv2d_bwd_data_t_ex (dgrad != 0)
  * runs this geometry on the resident-B kernel: the tile's activation operand split
  * into bf16 term images once and kept in LDS across the kernel taps, only the

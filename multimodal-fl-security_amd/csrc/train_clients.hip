@@ -800,7 +800,17 @@ class Net {
         if (ps_[bk.c1.p].tap && ps_[bk.ds.p].tap && o_.fuse_res) {
           // d_in = dgrad(c1), then the strided 1x1 shortcut's dgrad added in place
           // (its epilogue: dx = dgrad(ds) + dx, the same one fp32 add); the parity
-          // classes no shortcut tap reaches are skipped instead of written as zeros
+          // classes no shortcut tap reaches are skipped instead of written as zeros.
+          // Where the fused strided data gradient is taken, both are its one launch
+          // (the same bits) and the shortcut's conv_bwd only does dW
+          if (flr_conv2d_dgrad_fused_preferred(K_, B_, bk.c1.Cin, bk.c1.H, bk.c1.H, bk.c1.Cout, bk.c1.k, bk.c1.k,
+                                               bk.c1.stride, bk.c1.pad, 1) &&
+              bk.ds.stride == bk.c1.stride && bk.ds.k == 1 && bk.ds.pad == 0 && bk.ds.Cin == bk.c1.Cin &&
+              bk.ds.H == bk.c1.H) {
+            FLR_TRY(conv_bwd(S, bk.c1, bk.x_in, bk.d_y1, bk.d_in, st, nullptr, &bk.ds, bk.d_yd));
+            FLR_TRY(conv_bwd(S, bk.ds, bk.x_in, bk.d_yd, nullptr, st));
+            continue;
+          }
           FLR_TRY(conv_bwd(S, bk.c1, bk.x_in, bk.d_y1, bk.d_in, st));
           FLR_TRY(conv_bwd(S, bk.ds, bk.x_in, bk.d_yd, bk.d_in, st, bk.d_in));
           continue;
@@ -1022,12 +1032,15 @@ class Net {
   // forked here (dy ready on st), the data gradient on st.  The two write disjoint
   // outputs; dy and x are not rewritten this step.
   int conv_bwd(Step& S, const ConvOp& c, const float* x, const float* dy, float* dx, hipStream_t st,
-               const float* add = nullptr) {
+               const float* add = nullptr, const ConvOp* sc = nullptr, const float* dy_sc = nullptr) {
     const Param& p = ps_[c.p];
     int rc;
     if (p.tap) {
       int64_t wst;
       const float* w = tap_w(p, S.wsh, wst);
+      // sc: the block's tap-major 1x1 shortcut, its data gradient accumulated onto dx
+      int64_t wst_sc = 0;
+      const float* w_sc = sc ? tap_w(ps_[sc->p], S.wsh, wst_sc) : nullptr;
       hipStream_t ws = st;
       char* wsp = cws_;
       if (S.wg_on_text && S.tx.left(2)) {  // TX_WG_JOIN stays free
@@ -1039,8 +1052,9 @@ class Net {
         ws = o_.wgrad->s;
         wsp = cws2_;
       }
-      if (dx && (rc = flr_conv2d_bwd_data_t_ex(dy, w, wst, add, dx, K_, B_, c.Cin, c.H, c.H, c.Cout, c.k, c.k,
-                                               c.stride, c.pad, cws_, cws_n_, st)) != FLR_OK)
+      if (dx && (rc = flr_conv2d_bwd_data_t_sc(dy, w, wst, add, dx, K_, B_, c.Cin, c.H, c.H, c.Cout, c.k, c.k,
+                                               c.stride, c.pad, sc ? dy_sc : nullptr, w_sc, wst_sc,
+                                               sc ? sc->Cout : 0, cws_, cws_n_, st)) != FLR_OK)
         return rc;
       const int zero_dead = p.dead ? 0 : 1;
       if (p.sq_base >= 0)

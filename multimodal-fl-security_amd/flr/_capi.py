@@ -164,6 +164,11 @@ SIGNATURES = {
                                                                                           _c_void_p]),
     "flr_conv2d_bwd_data_t_ex": (_int, [_c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p] + [_i64] * 10 +
                                  [_c_void_p, _size_t, _c_void_p]),
+    "flr_conv2d_bwd_data_t_sc": (_int, [_c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p] + [_i64] * 10 +
+                                 [_c_void_p, _c_void_p, _i64, _i64, _c_void_p, _size_t, _c_void_p]),
+    "flr_conv2d_dgrad_fused_supported": (_int, [_i64] * 10),
+    "flr_conv2d_dgrad_fused_preferred": (_int, [_i64] * 10 + [_int]),
+    "flr_conv2d_dgrad_class_splits": (_int, [_i64] * 10 + [_int, _size_t]),
     "flr_conv2d_resident_ok": (_int, [_i64] * 10 + [_int]),
     "flr_conv2d_bwd_weight_t": (_int, [_c_void_p, _c_void_p, _c_void_p] + [_i64] * 10 + [_int, _c_void_p, _size_t,
                                                                                          _c_void_p]),

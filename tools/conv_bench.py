@@ -1,6 +1,8 @@
 """Per-layer timing of the client-batched conv kernels at the C3 shapes
 (K=128 clients, B=32): fwd / dgrad / wgrad, us and TFLOP/s (useful FLOPs of
-the valid taps).  usage: conv_bench.py [--only NAME] [--reps N] [--resident] [--variants "A=1,B=2;C=3"]
+the valid taps).  usage: conv_bench.py [--only NAME] [--reps N] [--resident] [--shortcut] [--variants "A=1,B=2;C=3"]
+--shortcut: a row "dg+ds" for l2a / l3a / l4a, the data gradient with the block's 1x1 shortcut folded in
+(flr_conv2d_bwd_data_t_sc: two per-class call sequences, or one launch under FLR_DGRAD_FUSED).
 --resident: columns for FLR_CONV_RESIDENT=0 | 1 | 0 | 1 (the resident-B form of layer1's fwd / dgrad), then
 for FLR_WGRAD_RESIDENT=0 | 1 | 0 | 1 (the resident form of layer1's weight gradient).
 --variants: extra env settings timed in the same process, interleaved with the
@@ -81,6 +83,13 @@ def main():
             "wgrad": lambda: _capi.call("flr_conv2d_bwd_weight" + sfx, x.data_ptr(), dy.data_ptr(), dw.data_ptr(),
                                         *geom, *((0,) if tm else ()), wsp, n, st),  # dead taps skipped, as in training
         }
+        if "--shortcut" in sys.argv and tm and s == 2 and k == 3:
+            dyd = torch.randn_like(y)
+            wd = torch.randn(K, Cout, Cin, 1, 1, device=dev) * 0.05
+            wst = k * k * Cin * Cout  # (k is rebound by the variant loop below)
+            calls["dg+ds"] = lambda: _capi.call("flr_conv2d_bwd_data_t_sc", dy.data_ptr(), w.data_ptr(),
+                                                wst, None, dx.data_ptr(), *geom, dyd.data_ptr(),
+                                                wd.data_ptr(), Cin * Cout, Cout, wsp, n, st)
         flops = 2.0 * K * B * Ho * Ho * Cout * Cin * nt
         for op, fn in calls.items():
             if name == "stem" and op == "dgrad":
