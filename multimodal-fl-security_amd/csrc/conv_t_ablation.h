@@ -1,9 +1,13 @@
 // The batched-GEMM kernel forms that were measured slower than split-at-stash
 // and the knobs that select them: the LDS-DMA form (dsgemm_kernel), the
 // pre-split form (presplit_kernel + psgemm_kernel) and transposed images for
-// k-contiguous operands.  Compiled into the tools build only (make ABLATION=1);
-// conv_t_kernels.h includes this file between its kernels and its launch code.
+// k-contiguous operands; with them the timing ablations of the split-at-stash
+// loop (FLR_SG_ABL) and the tgemm forms 1, 3 and 4.  Compiled into the tools
+// build only (make ABLATION=1): conv_t_kernels.h includes this file after its
+// kernels, and launch_tiles (conv_t_launch.h) asks launch_ablation() first.
 #pragma once
+
+#include <climits>
 
 namespace flr {
 namespace convt {
@@ -113,10 +117,7 @@ __global__ __launch_bounds__(THREADS, 2) void dsgemm_kernel(const Plan pl, int S
 // (vit.qkv 461 vs 391 us, vit.fc1 519 vs 489, vit.fc2 480 vs 455 at 32 clients;
 // profiles/r4_bgemm_dma_ab.txt): the per-wave split doubles the VALU split work
 // of the stash form, which costs more than the ds_write pass it removes.
-inline bool bgemm_dma() {
-  const char* e = flr::knob("FLR_BGEMM_DMA");
-  return e && e[0] == '1';
-}
+inline bool bgemm_dma() { return knob_on("FLR_BGEMM_DMA"); }
 // ---- the pre-split form (batched GEMMs with 128 x 128 tiles, FLR_BGEMM_PRESPLIT=1; measured slower) --
 // Each operand is split into bf16 hi / mid / lo ONCE per GEMM by presplit_kernel
 // (the same split3 as every other form) into k-contiguous planes in the
@@ -281,10 +282,7 @@ __global__ __launch_bounds__(THREADS, 2) void psgemm_kernel(const Plan pl, int S
 // tiles re-read their operands from L2 once per opposite tile, so the loop moves
 // 1.5x the bytes (2.8 GB per vit.qkv GEMM at 32 clients), and the split pass
 // itself transposes the row-contiguous (KR) operands of the weight gradients.
-inline bool bgemm_presplit() {
-  const char* e = flr::knob("FLR_BGEMM_PRESPLIT");
-  return e && e[0] == '1';
-}
+inline bool bgemm_presplit() { return knob_on("FLR_BGEMM_PRESPLIT"); }
 
 template <class P> struct dma_ok : std::false_type {};
 template <int A, int B> struct dma_ok<BGemm<A, B>> : std::integral_constant<bool, A != BM_G && B != BM_G> {};
@@ -300,9 +298,75 @@ template <int A, int B> struct is_bgemm_t<BGemm<A, B>> : std::true_type {
 // (A/B; off by default: the eight 4-B loads per thread cost more than the
 // quad-lane stash's 2-way bank conflicts save — vit.qkv 493 vs 426 us at K=32,
 // profiles/r3_bgemm_timg.txt)
-inline bool bgemm_timg() {
-  const char* e = flr::knob("FLR_BGEMM_TIMG");
-  return e && e[0] == '1';
+inline bool bgemm_timg() { return knob_on("FLR_BGEMM_TIMG"); }
+
+// launch_tiles' hook: runs the tools build's form the knobs select for this
+// launch, if any (true: launched).  form is gemm_form(); partp moves past the
+// planes when the pre-split form takes the front of the workspace.
+template <class Plan, int MS, int NS>
+bool launch_ablation(const Plan& pl, dim3 grid, int S, int form, void* ws, size_t ws_bytes, hipStream_t st,
+                     float*& partp) {
+  const int M = pl.M(), N = pl.N(), R = pl.R(), K = pl.g.Kc;
+  float* part = static_cast<float*>(ws);
+  if constexpr (is_bgemm_t<Plan>::ta || is_bgemm_t<Plan>::tb) {
+    // batched GEMMs with a k-contiguous operand: that operand on a transposed
+    // image (coalesced 128-B row reads, conflict-free stashes; the row-major
+    // image of a quad-lane load stashes 2-way bank-conflicted)
+    if (form == 5 && bgemm_timg()) {
+      hipLaunchKernelGGL((wsgemm_kernel<Plan, MS, NS, is_bgemm_t<Plan>::ta, is_bgemm_t<Plan>::tb>), grid,
+                         dim3(THREADS), 0, st, pl, S, part, xcd_remap());
+      return true;
+    }
+  }
+  if constexpr (std::is_base_of<BGemmArgs, Plan>::value && MS == 2 && NS == 2) {
+    if (form == 5 && bgemm_presplit()) {
+      const size_t pa_b = (ps_plane_bytes(K, M, R) + 255) / 256 * 256;
+      const size_t pb_b = (ps_plane_bytes(K, N, R) + 255) / 256 * 256;
+      const size_t need = pa_b + pb_b + (S > 1 ? (size_t)S * K * M * N * sizeof(float) : 0);
+      // the planes' byte offsets must fit the 31-bit buffer voffset
+      if (ws && ws_bytes >= need && pa_b < (size_t(1) << 31) && pb_b < (size_t(1) << 31)) {
+        __bf16* pa = static_cast<__bf16*>(ws);
+        __bf16* pb = reinterpret_cast<__bf16*>(static_cast<char*>(ws) + pa_b);
+        partp = reinterpret_cast<float*>(static_cast<char*>(ws) + pa_b + pb_b);
+        const int Mp = (int)ps_pad(M, PS_ROWS), Np = (int)ps_pad(N, PS_ROWS), Rp = (int)ps_pad(R, BK);
+        auto pgrid = [](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384))); };
+        hipLaunchKernelGGL((presplit_kernel<Plan::AMODE>), pgrid((int64_t)K * Mp * Rp / 8), dim3(THREADS), 0, st, pl.a,
+                           pl.a_k, pl.a_m, pl.a_r, K, M, R, Mp, Rp, pa);
+        hipLaunchKernelGGL((presplit_kernel<Plan::BMODE>), pgrid((int64_t)K * Np * Rp / 8), dim3(THREADS), 0, st, pl.b,
+                           pl.b_k, pl.b_n, pl.b_r, K, N, R, Np, Rp, pb);
+        hipLaunchKernelGGL((psgemm_kernel<Plan>), grid, dim3(THREADS), 0, st, pl, S, partp, xcd_remap(), pa, pb, Mp,
+                           Np, Rp);
+        return true;
+      }
+    }
+  }
+  if constexpr (dma_ok<Plan>::value && MS == 2 && NS == 2) {
+    if (form == 5 && bgemm_dma()) {
+      hipLaunchKernelGGL((dsgemm_kernel<Plan>), grid, dim3(THREADS), 0, st, pl, S, part, xcd_remap());
+      return true;
+    }
+  }
+  if constexpr (has_k8<Plan>::value && MS == 2 && NS == 2) {
+    const int abl = knob_int("FLR_SG_ABL", INT_MIN, INT_MAX, 0);  // timing ablations of the main loop
+#define FLR_SG_ABL_CASE(A)                                                                                      \
+  if (form == 5 && abl == A) {                                                                                   \
+    hipLaunchKernelGGL((sgemm_kernel<Plan, MS, NS, A>), grid, dim3(THREADS), 0, st, pl, S, part, xcd_remap()); \
+    return true;                                                                                                 \
+  }
+    FLR_SG_ABL_CASE(1) FLR_SG_ABL_CASE(2) FLR_SG_ABL_CASE(3) FLR_SG_ABL_CASE(4) FLR_SG_ABL_CASE(8)
+    FLR_SG_ABL_CASE(10) FLR_SG_ABL_CASE(16) FLR_SG_ABL_CASE(11) FLR_SG_ABL_CASE(15) FLR_SG_ABL_CASE(23)
+#undef FLR_SG_ABL_CASE
+  }
+  // 1: accumulator-chain order; 3: one bf16 term, no split (wrong results); 4: the unpipelined loop
+#define FLR_TG_FORM(F)                                                                                            \
+  if (form == F) {                                                                                                 \
+    hipLaunchKernelGGL((tgemm_kernel<Plan, MS, NS, F>), grid, dim3(THREADS), 0, st, pl, S, part, xcd_remap(),    \
+                       mfma_prio());                                                                               \
+    return true;                                                                                                   \
+  }
+  FLR_TG_FORM(1) FLR_TG_FORM(3) FLR_TG_FORM(4)
+#undef FLR_TG_FORM
+  return false;
 }
 
 }  // namespace convt

@@ -8,7 +8,7 @@
 // dgrad_classes' order — it runs sgemm_body's K-loop with that class's DgradT
 // plan: the same init8 / load_a8 / load_b8, K-tile order, k-steps and six
 // products per accumulator.  Where the per-class launch takes split-K S > 1
-// (dgrad_class_splits: launch()'s own choice), the S ranges of K-tiles run one
+// (resolve()'s S for that class and workspace), the S ranges of K-tiles run one
 // after another into a fresh accumulator each and are summed in
 // treduce_kernel's order (part 0, + part 1, ...): the same bits, no partial
 // written, no reduce launch.  The optional shortcut (the block's 1x1 / 2
@@ -22,7 +22,7 @@
 // the lanes of a class row then write a whole contiguous row of dx.
 #pragma once
 
-#include "conv_t_kernels.h"
+#include "conv_t_launch.h"
 
 namespace flr {
 namespace convt {
@@ -228,23 +228,6 @@ __global__ __launch_bounds__(THREADS, SG_OCC) void fdgrad_kernel(const DgradFuse
   }
 }
 
-// The split-K count launch() takes for one parity class given this workspace
-// (the narrow launch and the fill tiles split by their default tile's count).
-inline int dgrad_class_splits(const DgradT& pl, const void* ws, size_t ws_bytes) {
-  const int M = pl.M(), N = pl.N(), R = pl.R(), K = pl.g.Kc;
-  if (R == 0) return 1;
-  int sub;
-  if (N <= 32 && M % (2 * BM) == 0 && gemm_form() == 5 && conv_narrow()) {
-    sub = 2;
-  } else {
-    const int tile = plan_tile(pl);
-    sub = (tile / 10) * (tile % 10);
-  }
-  int S = choose_splits(M, N, R, K, sub, plan_min_kt(pl));
-  if (S > 1 && (!ws || ws_bytes < (size_t)S * K * M * N * sizeof(float))) S = 1;
-  return S;
-}
-
 // FLR_DGRAD_FUSED (read per launch): 0 = the per-class launches, 1 = the fused
 // kernel wherever eligible, unset = the per-shape preference below.
 inline int dgrad_fused_knob() {
@@ -263,7 +246,7 @@ inline bool dgrad_fused_geom_ok(const Geom& g) {
 // class): the narrow tile (code 20) where a class has at most 32 columns (l4a),
 // 64 x 128 (12) for 64 input channels (l2a), else 64 x 64 (11) — and the grid.
 inline int fd_tile(int M, int N) {
-  if (N <= 32 && M % (2 * BM) == 0 && conv_narrow()) return 20;
+  if (narrow_shape(M, N)) return 20;
   return M == BM && N % (2 * BN) == 0 ? 12 : 11;
 }
 // The two class rows of a tile in two workgroups (fdgrad_kernel's rows): taken for the

@@ -4,7 +4,7 @@
 // stash), rgemm_kernel (the activation tile resident in LDS across the taps:
 // layer1), wsgemm_kernel (transposed images: the weight gradient), rwgemm_kernel
 // (the weight gradient with x and dy staged once for three taps: layer1),
-// treduce_kernel (split-K), then the tile / split-K policy and launch().
+// treduce_kernel (split-K).  conv_t_launch.h decides which of them a launch runs.
 #pragma once
 
 #include "conv_t_plans.h"
@@ -1139,442 +1139,9 @@ __global__ void treduce_kernel(const Plan pl, int S, const float* __restrict__ p
   }
 }
 
-#ifdef FLR_ABLATION
 }  // namespace convt
 }  // namespace flr
+
+#ifdef FLR_ABLATION
 #include "conv_t_ablation.h"  // the tools build's kernel forms: they use the epilogue above
-namespace flr {
-namespace convt {
 #endif
-
-// Split-K count from the PER-CLIENT problem only (never the client count K):
-// a client's reduction order — and so its trained weights — must not depend
-// on how many clients share its GPU (bit-identical results at 1/2/4/8 GPUs).
-// 16 tiles per client = the 2048-workgroup target at the nominal 128 clients.
-// min_kt: fewest K-tiles a split may keep (8 for the convolutions; the batched
-// GEMMs read FLR_BGEMM_MINKT, default 32: 8 cost 1.7 ms per C3 round in split-K partials and reduce passes).
-inline int choose_splits(int M, int N, int R, int /*K*/, int sub = 1, int min_kt = 8) {
-  const int tiles = cdiv(M, BM) * cdiv(N, BN) / sub;
-  const int ktiles = cdiv(R, BK);
-  int S = 1;
-  while (S < 16 && tiles * S < 16 && ktiles / (2 * S) >= min_kt) S *= 2;
-  return S;
-}
-
-inline int bgemm_min_kt() {
-  static const int v = [] {
-    const char* e = flr::knob("FLR_BGEMM_MINKT");
-    const int x = e ? atoi(e) : 0;
-    return x >= 1 && x <= 64 ? x : 32;
-  }();
-  return v;
-}
-
-// Fewest K-tiles per conv split-K part.  32 (measured per layer against 8 and 16,
-// tools/conv_bench.py): a workgroup's unhidden prologue (first load, split,
-// barrier) amortises over more K-tiles; the l3b / l4 forward and dgrad gain the
-// most.  FLR_CONV_MINKT overrides (A/B timing).
-inline int conv_min_kt() {
-  static const int v = [] {
-    const char* e = flr::knob("FLR_CONV_MINKT");
-    const int x = e ? atoi(e) : 0;
-    return x >= 1 && x <= 256 ? x : 32;
-  }();
-  return v;
-}
-
-// Stride-1 dgrad (one class: the forward's GEMM shape, transposed) takes the
-// forward's split rule unless FLR_DGRAD_MINKT1 overrides it (A/B timing).
-inline int dgrad_min_kt1() {
-  static const int v = [] {
-    const char* e = flr::knob("FLR_DGRAD_MINKT1");
-    const int x = e ? atoi(e) : 0;
-    return x >= 1 && x <= 256 ? x : 0;
-  }();
-  return v ? v : conv_min_kt();
-}
-
-// Strided dgrad classes (FLR_DGRAD_MINKT2 overrides 8 for A/B timing).
-inline int dgrad_min_kt2() {
-  static const int v = [] {
-    const char* e = flr::knob("FLR_DGRAD_MINKT2");
-    const int x = e ? atoi(e) : 0;
-    return x >= 1 && x <= 256 ? x : 8;
-  }();
-  return v;
-}
-
-template <class Plan>
-inline int plan_min_kt(const Plan& pl) {
-  if (std::is_base_of<BGemmArgs, Plan>::value) return bgemm_min_kt();
-  // a strided dgrad's parity class has few tiles per client (l3a: one 128 x 128
-  // tile): it keeps the deeper split-K, or the launch runs ~128 workgroups on 256 CUs
-  if constexpr (std::is_same<Plan, DgradT>::value) return pl.g.stride == 1 ? dgrad_min_kt1() : dgrad_min_kt2();
-  return conv_min_kt();
-}
-
-template <class Plan>
-size_t splits_bytes(const Plan& pl) {  // enough for any sub-tile count (1, 2, 3, 4)
-  int S = 1;
-  for (int sub : {1, 2, 3, 4}) S = std::max(S, choose_splits(pl.M(), pl.N(), pl.R(), pl.g.Kc, sub, plan_min_kt(pl)));
-  return S > 1 ? (size_t)S * pl.g.Kc * pl.M() * pl.N() * sizeof(float) : 0;
-}
-
-// Workgroup tile: 64 x 64 (MS = NS = 1: 4 waves of 32 x 32, 4 workgroups/CU)
-// or 128 x 128 (MS = NS = 2: each wave 64 x 64, its A and B fragments — and
-// their bf16 splits — reused twice; 2 workgroups/CU).  Measured per ResNet-18
-// layer on MI355X (tools/conv_bench.py): 128 x 128 wins where both dimensions
-// allow it and the tile still has work — a reduction of >= 512 or more than
-// 128 x 512 outputs per client; 64 x 64 everywhere else.
-// FLR_CONV_TILE=11|21|12|22 forces a shape (read per launch, for A/B runs).
-inline int tile_choice(int M, int N, int R) {
-  const char* e = flr::knob("FLR_CONV_TILE");
-  const int forced = e ? atoi(e) : 0;
-  if (forced == 11) return 11;
-  if (forced == 21 && M % 128 == 0) return 21;
-  if (forced == 12 && N % 128 == 0) return 12;
-  const bool big = M % 128 == 0 && N % 128 == 0;
-  if (forced == 22 && big) return 22;
-  if (forced == 0 && big && (R >= 512 || (int64_t)M * N > 128 * 512)) return 22;
-  return 11;
-}
-
-template <class Plan, int MS, int NS>
-int launch_tiles(const Plan& pl, void* ws, size_t ws_bytes, hipStream_t st, const char* name, int split_sub = 0,
-                 bool wres = false) {
-  const int M = pl.M(), N = pl.N(), R = pl.R(), K = pl.g.Kc;
-  // split_sub: the sub-tile count the split-K choice is made for (0: this tile's);
-  // a launch on smaller tiles with the default tile's split count computes the
-  // same sums in the same order (fill_tile below)
-  int S = choose_splits(M, N, R, K, split_sub > 0 ? split_sub : MS * NS, plan_min_kt(pl));
-  if (S > 1 && (!ws || ws_bytes < (size_t)S * K * M * N * sizeof(float))) {
-    // a clip-norm launch must write the slots sq_slots() promised: no silent fallback
-    if constexpr (has_sq<Plan>::value) {
-      if (pl.sq) return FLR_ERR_WORKSPACE;
-    }
-    S = 1;
-  }
-  const dim3 grid((unsigned)cdiv(N, BN * NS), (unsigned)cdiv(M, BM * MS), (unsigned)(K * S));
-  int form = gemm_form();
-  float* partp = static_cast<float*>(ws);  // split-K partials (after the planes in the pre-split form)
-#ifdef FLR_ABLATION  // the measured-slower batched-GEMM forms: tools build only
-  if constexpr (is_bgemm_t<Plan>::ta || is_bgemm_t<Plan>::tb) {
-    // batched GEMMs with a k-contiguous operand: that operand on a transposed
-    // image (coalesced 128-B row reads, conflict-free stashes; the row-major
-    // image of a quad-lane load stashes 2-way bank-conflicted)
-    if (form == 5 && bgemm_timg()) {
-      hipLaunchKernelGGL((wsgemm_kernel<Plan, MS, NS, is_bgemm_t<Plan>::ta, is_bgemm_t<Plan>::tb>), grid,
-                         dim3(THREADS), 0, st, pl, S, static_cast<float*>(ws), xcd_remap());
-      form = -1;
-    }
-  }
-  if constexpr (std::is_base_of<BGemmArgs, Plan>::value && MS == 2 && NS == 2) {
-    if (form == 5 && bgemm_presplit()) {
-      const size_t pa_b = (ps_plane_bytes(K, M, R) + 255) / 256 * 256;
-      const size_t pb_b = (ps_plane_bytes(K, N, R) + 255) / 256 * 256;
-      const size_t need = pa_b + pb_b + (S > 1 ? (size_t)S * K * M * N * sizeof(float) : 0);
-      // the planes' byte offsets must fit the 31-bit buffer voffset
-      if (ws && ws_bytes >= need && pa_b < (size_t(1) << 31) && pb_b < (size_t(1) << 31)) {
-        __bf16* pa = static_cast<__bf16*>(ws);
-        __bf16* pb = reinterpret_cast<__bf16*>(static_cast<char*>(ws) + pa_b);
-        partp = reinterpret_cast<float*>(static_cast<char*>(ws) + pa_b + pb_b);
-        const int Mp = (int)ps_pad(M, PS_ROWS), Np = (int)ps_pad(N, PS_ROWS), Rp = (int)ps_pad(R, BK);
-        auto pgrid = [](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 16384))); };
-        hipLaunchKernelGGL((presplit_kernel<Plan::AMODE>), pgrid((int64_t)K * Mp * Rp / 8), dim3(THREADS), 0, st, pl.a,
-                           pl.a_k, pl.a_m, pl.a_r, K, M, R, Mp, Rp, pa);
-        hipLaunchKernelGGL((presplit_kernel<Plan::BMODE>), pgrid((int64_t)K * Np * Rp / 8), dim3(THREADS), 0, st, pl.b,
-                           pl.b_k, pl.b_n, pl.b_r, K, N, R, Np, Rp, pb);
-        hipLaunchKernelGGL((psgemm_kernel<Plan>), grid, dim3(THREADS), 0, st, pl, S, partp, xcd_remap(), pa, pb, Mp,
-                           Np, Rp);
-        form = -1;
-      }
-    }
-  }
-  if constexpr (dma_ok<Plan>::value && MS == 2 && NS == 2) {
-    if (form == 5 && bgemm_dma()) {
-      hipLaunchKernelGGL((dsgemm_kernel<Plan>), grid, dim3(THREADS), 0, st, pl, S, static_cast<float*>(ws),
-                         xcd_remap());
-      form = -1;
-    }
-  }
-#endif
-  if constexpr (has_k8<Plan>::value) {
-#ifdef FLR_ABLATION
-    if constexpr (MS == 2 && NS == 2) {
-      const char* ae = flr::knob("FLR_SG_ABL");  // timing ablations of the main loop (tools build only)
-      const int abl = ae ? atoi(ae) : 0;
-#define FLR_SG_ABL_CASE(A)                                                                                  \
-  if (form == 5 && abl == A) {                                                                               \
-    hipLaunchKernelGGL((sgemm_kernel<Plan, MS, NS, A>), grid, dim3(THREADS), 0, st, pl, S,               \
-                       static_cast<float*>(ws), xcd_remap());                                                \
-    form = -1;                                                                                               \
-  }
-      FLR_SG_ABL_CASE(1) FLR_SG_ABL_CASE(2) FLR_SG_ABL_CASE(3) FLR_SG_ABL_CASE(4) FLR_SG_ABL_CASE(8)
-      FLR_SG_ABL_CASE(10) FLR_SG_ABL_CASE(16) FLR_SG_ABL_CASE(11) FLR_SG_ABL_CASE(15) FLR_SG_ABL_CASE(23)
-#undef FLR_SG_ABL_CASE
-    }
-#endif
-    if (form == 5) {
-      hipLaunchKernelGGL((sgemm_kernel<Plan, MS, NS>), grid, dim3(THREADS), 0, st, pl, S, static_cast<float*>(ws),
-                         xcd_remap());
-      form = -1;
-    }
-  }
-  if constexpr (std::is_same<Plan, WgtT<true>>::value && MS == 1 && NS == 1) {
-    if (form == 5 && wres) {  // wgrad_resident_ok: the same split count, partials and treduce pass
-      const dim3 rgrid(1u, (unsigned)(pl.g.ntaps / RW_TG), (unsigned)(K * S));
-      hipLaunchKernelGGL((rwgemm_kernel<Plan, RW_TG>), rgrid, dim3(THREADS), 0, st, pl, S, static_cast<float*>(ws),
-                         xcd_remap());
-      form = -1;
-    }
-  }
-  if constexpr (std::is_same<Plan, WgtT<true>>::value || std::is_same<Plan, WgtT<false>>::value) {
-    if (form == 5) {
-      hipLaunchKernelGGL((wsgemm_kernel<Plan, MS, NS, true, true>), grid, dim3(THREADS), 0, st, pl, S,
-                         static_cast<float*>(ws), xcd_remap());
-      form = -1;
-    }
-  }
-  if (form == 5) form = 2;  // plans without k8 loads
-  switch (form) {  // every form keeps each accumulator's product order: results do not depend on it
-    case -1:
-      break;
-    case 0:
-      hipLaunchKernelGGL((tgemm_kernel<Plan, MS, NS, 0>), grid, dim3(THREADS), 0, st, pl, S,
-                         static_cast<float*>(ws), xcd_remap(), mfma_prio());
-      break;
-#ifdef FLR_ABLATION
-    case 1:
-      hipLaunchKernelGGL((tgemm_kernel<Plan, MS, NS, 1>), grid, dim3(THREADS), 0, st, pl, S,
-                         static_cast<float*>(ws), xcd_remap(), mfma_prio());
-      break;
-    case 3:
-      hipLaunchKernelGGL((tgemm_kernel<Plan, MS, NS, 3>), grid, dim3(THREADS), 0, st, pl, S,
-                         static_cast<float*>(ws), xcd_remap(), mfma_prio());
-      break;
-    case 4:
-      hipLaunchKernelGGL((tgemm_kernel<Plan, MS, NS, 4>), grid, dim3(THREADS), 0, st, pl, S,
-                         static_cast<float*>(ws), xcd_remap(), mfma_prio());
-      break;
-#endif
-    default:
-      hipLaunchKernelGGL((tgemm_kernel<Plan, MS, NS, 2>), grid, dim3(THREADS), 0, st, pl, S,
-                         static_cast<float*>(ws), xcd_remap(), mfma_prio());
-  }
-  int rc = launch_status(name);
-  if (rc != FLR_OK || S == 1) return rc;
-  const int64_t mn = (int64_t)M * N;
-  hipLaunchKernelGGL(treduce_kernel<Plan>, dim3((unsigned)((mn + 255) / 256), (unsigned)K), dim3(256), 0, st, pl, S,
-                     static_cast<const float*>(partp));
-  return launch_status(name);
-}
-
-// Tile code 10 * MS + NS.  Besides the square shapes above, the tap-major
-// convolutions take 64 x 192 / 192 x 64 (13 / 31) and 64 x 256 / 256 x 64
-// (14 / 41): a 64-row operand (layer1's 64 channels) then feeds three or four
-// MFMA sub-tiles per fragment read instead of one or two (LDS: five sub-tiles
-// of bf16 images, still two workgroups per CU).
-template <class Plan>
-constexpr bool wide_tiles() {
-  return std::is_same<Plan, FwdT>::value || std::is_same<Plan, DgradT>::value ||
-         std::is_same<Plan, WgtT<true>>::value || std::is_same<Plan, WgtT<false>>::value;
-}
-
-template <class Plan>
-inline int plan_tile(const Plan& pl) {
-  const int M = pl.M(), N = pl.N(), R = pl.R();
-  const char* e = flr::knob("FLR_CONV_TILE");
-  const int forced = e ? atoi(e) : 0;
-  if (forced) {  // A/B timing: any shape that leaves no sub-tile empty
-    const int ms = forced / 10, ns = forced % 10;
-    const bool ok = ms >= 1 && ns >= 1 && ms * ns <= 4 && (wide_tiles<Plan>() || (ms <= 2 && ns <= 2)) &&
-                    M > 64 * (ms - 1) && N > 64 * (ns - 1);
-    if (ok) return forced;
-  }
-  int tile = tile_choice(M, N, R);
-  // dgrad with 64 input channels (layer1): 64 x 128 tiles, the A fragment feeding
-  // two B sub-tiles (measured 178 -> 147 us at l1)
-  if (std::is_same<Plan, DgradT>::value && tile == 11 && M == 64 && N % 128 == 0) tile = 12;
-  return tile;
-}
-
-// Clip-norm partial slots per client a WgtT launch writes (the tile count at
-// split-K 1, else one per 256-value treduce block), under the launch's own
-// tile and split choice — given a workspace of splits_bytes(pl).
-template <class Plan>
-int sq_slots(const Plan& pl) {
-  const int M = pl.M(), N = pl.N(), R = pl.R();
-  const int tile = plan_tile(pl);
-  const int ms = tile / 10, ns = tile % 10;
-  const int S = choose_splits(M, N, R, pl.g.Kc, ms * ns, plan_min_kt(pl));
-  if (S == 1) return cdiv(N, BN * ns) * cdiv(M, BM * ms);
-  return (int)(((int64_t)M * N + 255) / 256);
-}
-
-// Narrow-N tiles (sgemm_body NAR) for the conv forward / data gradient whose GEMM has
-// at most 32 columns (the l4 layers at 32 x 32 inputs: B * 1 * 1); FLR_CONV_NARROW=0:
-// the 64-wide tiles (A/B, read per launch).
-inline bool conv_narrow() {
-  const char* e = flr::knob("FLR_CONV_NARROW");
-  return !(e && e[0] == '0');
-}
-template <class Plan>
-int launch_narrow(const Plan& pl, void* ws, size_t ws_bytes, hipStream_t st, const char* name) {
-  const int M = pl.M(), N = pl.N(), R = pl.R(), K = pl.g.Kc;
-  int S = choose_splits(M, N, R, K, 2, plan_min_kt(pl));
-  if (S > 1 && (!ws || ws_bytes < (size_t)S * K * M * N * sizeof(float))) S = 1;
-  const dim3 grid((unsigned)cdiv(N, BN), (unsigned)cdiv(M, 2 * BM), (unsigned)(K * S));
-  hipLaunchKernelGGL((sgemm_kernel<Plan, 2, 1, 0, true>), grid, dim3(THREADS), 0, st, pl, S,
-                     static_cast<float*>(ws), xcd_remap());
-  int rc = launch_status(name);
-  if (rc != FLR_OK || S == 1) return rc;
-  const int64_t mn = (int64_t)M * N;
-  hipLaunchKernelGGL(treduce_kernel<Plan>, dim3((unsigned)((mn + 255) / 256), (unsigned)K), dim3(256), 0, st, pl, S,
-                     static_cast<const float*>(ws));
-  return launch_status(name);
-}
-
-// Small client counts (K/G clients per GPU at G = 8: 16 at C3) leave the
-// default tiles' grids below one wave of the chip: layer2 / layer3 of ResNet-18
-// launch 4 workgroups of 128 x 128 per client.  Forward and data-gradient
-// launches whose grid would hold fewer than FILL_WG workgroups then run on
-// 64 x 64 tiles with the DEFAULT tile's split-K count: every output element is
-// the same K-tile / k-step / product sequence, so the result is bit-identical
-// to the default tiles (and the model to the one at G = 1).  The weight
-// gradients keep their tiles: their clip-norm partial slots follow the tile.
-// FLR_CONV_FILL=0: off (A/B, read per launch).
-constexpr int FILL_WG = 512;  // two 128 x 128 workgroups per CU on 256 CUs
-inline bool conv_fill() {
-  const char* e = flr::knob("FLR_CONV_FILL");
-  return !(e && e[0] == '0');
-}
-template <class Plan>
-bool fill_tile(const Plan& pl, int tile) {
-  if constexpr (!(std::is_same<Plan, FwdT>::value || std::is_same<Plan, DgradT>::value)) {
-    return false;
-  } else {
-    const int ms = tile / 10, ns = tile % 10;
-    if (ms * ns == 1 || !conv_fill()) return false;
-    const int M = pl.M(), N = pl.N(), R = pl.R();
-    const int S = choose_splits(M, N, R, pl.g.Kc, ms * ns, plan_min_kt(pl));
-    const int64_t wg = (int64_t)pl.g.Kc * cdiv(M, BM * ms) * cdiv(N, BN * ns) * S;
-    return wg < FILL_WG;
-  }
-}
-
-// The resident-B form (rgemm_kernel) for the forward and the stride-1 data gradient of
-// a "same" convolution with 64 output rows and 64 reduction channels whose images
-// tile 128 columns (layer1 of ResNet-18), where the default tile's split-K count is
-// 1 — the bits are the default path's.  FLR_CONV_RESIDENT=0: off (A/B, read per launch).
-inline bool conv_resident() {
-  const char* e = flr::knob("FLR_CONV_RESIDENT");
-  return !(e && e[0] == '0');
-}
-template <class Plan>
-bool resident_ok(const Plan& pl) {
-  if constexpr (!(std::is_same<Plan, FwdT>::value || std::is_same<Plan, DgradT>::value)) {
-    return false;
-  } else {
-    const Geom& g = pl.g;
-    if (!conv_resident() || gemm_form() != 5) return false;
-    if (g.stride != 1 || g.Ho != g.H || g.Wo != g.W) return false;
-    if (pl.M() != BM || pl.Cr() != 2 * BK) return false;
-    const int hw = g.H * g.W;
-    if (hw > RES_N || RES_N % hw != 0) return false;
-    if (pl.R() < 2 * pl.Cr()) return false;  // one tap: nothing is staged twice
-    const int tile = plan_tile(pl);
-    return choose_splits(pl.M(), pl.N(), pl.R(), g.Kc, (tile / 10) * (tile % 10), plan_min_kt(pl)) == 1;
-  }
-}
-template <class Plan>
-int launch_resident(const Plan& pl, hipStream_t st, const char* name) {
-  const dim3 grid((unsigned)cdiv(pl.N(), RES_N), 1u, (unsigned)pl.g.Kc);
-  hipLaunchKernelGGL((rgemm_kernel<Plan>), grid, dim3(THREADS), 0, st, pl, xcd_remap());
-  return launch_status(name);
-}
-
-// The resident weight gradient (rwgemm_kernel) for a stride-1 "same" convolution with
-// 64 channels on both sides (one 64 x 64 tile per tap: layer1 of ResNet-18) whose
-// images tile the 64-pixel chunk and whose live taps form whole groups of RW_TG.  The
-// tile, the split count, the partials and the clip-norm slots are the default
-// path's, and so are the bits.  FLR_WGRAD_RESIDENT=0: off (A/B, read per launch).
-inline bool wgrad_resident() {
-  const char* e = flr::knob("FLR_WGRAD_RESIDENT");
-  return !(e && e[0] == '0');
-}
-template <class Plan>
-bool wgrad_resident_ok(const Plan& pl) {
-  if constexpr (!std::is_same<Plan, WgtT<true>>::value) {
-    return false;  // H W % 4 != 0 (WgtT<false>) keeps the default kernel
-  } else {
-    const Geom& g = pl.g;
-    if (!wgrad_resident() || gemm_form() != 5) return false;
-    if (g.stride != 1 || g.Ho != g.H || g.Wo != g.W) return false;
-    if (g.Cin != BM || g.Cout != BN) return false;
-    if (g.ntaps < 2 || g.ntaps % RW_TG != 0) return false;  // one tap: nothing is staged twice
-    if (RW_PIX % (g.H * g.W) != 0) return false;
-    return pl.R() > 0 && plan_tile(pl) == 11;
-  }
-}
-
-template <class Plan>
-int launch(const Plan& pl, void* ws, size_t ws_bytes, hipStream_t st, const char* name) {
-  if (pl.R() == 0 && !std::is_same<Plan, DgradT>::value) return FLR_OK;  // a dgrad class with no tap stores zeros
-  if constexpr (std::is_same<Plan, WgtT<true>>::value) {
-    if (wgrad_resident_ok(pl)) return launch_tiles<Plan, 1, 1>(pl, ws, ws_bytes, st, name, 0, true);
-  }
-  if constexpr (std::is_same<Plan, FwdT>::value || std::is_same<Plan, DgradT>::value) {
-    if (resident_ok(pl)) return launch_resident(pl, st, name);
-  }
-  if constexpr (std::is_same<Plan, FwdT>::value || std::is_same<Plan, DgradT>::value) {
-    if (pl.N() <= 32 && pl.M() % (2 * BM) == 0 && pl.R() > 0 && gemm_form() == 5 && conv_narrow()) {
-      // a narrow launch under one wave of the chip (few clients per GPU): the 64 x 64
-      // tiles with the narrow tiles' split count — twice the workgroups, the same bits
-      const int S = choose_splits(pl.M(), pl.N(), pl.R(), pl.g.Kc, 2, plan_min_kt(pl));
-      if (conv_fill() && (int64_t)pl.g.Kc * cdiv(pl.M(), 2 * BM) * S < FILL_WG / 2)
-        return launch_tiles<Plan, 1, 1>(pl, ws, ws_bytes, st, name, 2);
-      return launch_narrow(pl, ws, ws_bytes, st, name);
-    }
-  }
-  const int tile = plan_tile(pl);
-  if (fill_tile(pl, tile)) return launch_tiles<Plan, 1, 1>(pl, ws, ws_bytes, st, name, (tile / 10) * (tile % 10));
-  if constexpr (wide_tiles<Plan>()) {
-    switch (tile) {
-      case 13: return launch_tiles<Plan, 1, 3>(pl, ws, ws_bytes, st, name);
-      case 31: return launch_tiles<Plan, 3, 1>(pl, ws, ws_bytes, st, name);
-      case 14: return launch_tiles<Plan, 1, 4>(pl, ws, ws_bytes, st, name);
-      case 41: return launch_tiles<Plan, 4, 1>(pl, ws, ws_bytes, st, name);
-      default: break;
-    }
-  }
-  switch (tile) {
-    case 21: return launch_tiles<Plan, 2, 1>(pl, ws, ws_bytes, st, name);
-    case 12: return launch_tiles<Plan, 1, 2>(pl, ws, ws_bytes, st, name);
-    case 22: return launch_tiles<Plan, 2, 2>(pl, ws, ws_bytes, st, name);
-    default: return launch_tiles<Plan, 1, 1>(pl, ws, ws_bytes, st, name);
-  }
-}
-
-inline bool shape_ok(int64_t Cin, int64_t Cout) { return Cin % 64 == 0 && Cout % 64 == 0; }
-
-inline bool args_ok(int64_t K, int64_t B, int64_t Cin, int64_t H, int64_t W, int64_t Cout, int64_t KH, int64_t KW,
-                    int64_t stride, int64_t pad) {
-  if (!conv::geom_ok(K, B, Cin, H, W, Cout, KH, KW, stride, pad) || !shape_ok(Cin, Cout)) return false;
-  // byte offsets inside one client's buffer view must fit the 31-bit voffset
-  if (!(B * K * Cin * H * W * 4 < (int64_t(1) << 31) && B * K * Cout * H * W * 4 < (int64_t(1) << 31) &&
-        KH * KW * Cin * Cout * 4 < (int64_t(1) << 31)))
-    return false;
-  // the kernels decode taps by rectangle arithmetic (true for any stride <= 4
-  // conv whose live rows / columns are contiguous: every ResNet shape)
-  if (stride > 4) return false;
-  const conv::Geom g = conv::make_geom(K, B, Cin, H, W, Cout, KH, KW, stride, pad);
-  if (!g.rect.ok) return false;
-  DgradT cls[MAX_CLASSES];
-  const int nc = dgrad_classes(g, cls);
-  for (int c = 0; c < nc; ++c)
-    if (!cls[c].crect.ok) return false;
-  return true;
-}
-
-}  // namespace convt
-}  // namespace flr

@@ -25,11 +25,12 @@
 // buffered LDS, deterministic split-K for long reductions (partials reduced
 // in split order).
 //
-// The code lives in four headers and five translation units:
+// The code lives in five headers and five translation units:
 //   conv_t_prims.h     (this file) buffer loads, fp32 LDS images, the bf16 split, knobs
 //   conv_t_plans.h     the load plans: FwdT, DgradT, WgtT, Dense*, Stem*, BGemm
-//   conv_t_kernels.h   the epilogue, the GEMM kernels, the tile / split-K policy, launch
-//   conv_t_ablation.h  the measured-slower batched-GEMM forms (make ABLATION=1 only)
+//   conv_t_kernels.h   the epilogue and the GEMM kernels
+//   conv_t_launch.h    the launch policy (form, tile, split-K: resolve) and launch
+//   conv_t_ablation.h  the measured-slower and timing-only forms (make ABLATION=1 only)
 //   train_conv_t_{im2col,fwd,dgrad,wgrad,bgemm}.hip   the extern "C" entry points;
 //   each unit instantiates only the kernels its entry points launch.
 #pragma once
@@ -175,12 +176,10 @@ __device__ __forceinline__ void split3(const float (&v)[8], bf16x8& hi, bf16x8& 
 // FLR_GEMM_STAGGER = n, workgroups of odd XCD slot start n x 512 cycles late;
 // bit 16 FLR_GEMM_SPRIO=1, those workgroups at s_setprio 1 for the whole loop
 inline int xcd_remap() {
-  const char* e = flr::knob("FLR_XCD");
-  int r = (e && e[0] == '0') ? 0 : 1;
+  int r = knob_off("FLR_XCD") ? 0 : 1;
   const char* st = flr::knob("FLR_GEMM_STAGGER");
   if (st) r |= (std::min(255, std::max(0, atoi(st))) << 8);
-  const char* sp = flr::knob("FLR_GEMM_SPRIO");
-  if (sp && sp[0] == '1') r |= 1 << 16;
+  if (knob_on("FLR_GEMM_SPRIO")) r |= 1 << 16;
   return r;
 }
 // the A/B controls above, at the start of a split-at-stash kernel
@@ -193,8 +192,7 @@ __device__ __forceinline__ void odd_slot_controls(int remap) {
 
 // Wave priority raised around each MFMA cluster (FLR_PRIO=0: off, for A/B).
 inline int mfma_prio() {  // measured +0-5 % on the encoder GEMMs and the 3x3 convs (FLR_PRIO=0 turns it off)
-  const char* e = flr::knob("FLR_PRIO");
-  return (e && e[0] == '0') ? 0 : 1;
+  return knob_off("FLR_PRIO") ? 0 : 1;
 }
 
 // 0: exact f32 MFMA; 2: bf16x6, product-major, software-pipelined; 5 (default):

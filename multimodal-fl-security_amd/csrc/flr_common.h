@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
 
 #include "../../include/flr.h"
 
@@ -15,6 +16,21 @@ void set_last_error(const char* where, hipError_t e);
 // An A/B switch's value (the FLR_* environment read once at library load, or
 // flr_set_knob since), nullptr when unset (capi.cpp).
 const char* knob(const char* name);
+// The usual readings: "0..." turns a default-on path off, "1..." a default-off
+// one on; an integer in [lo, hi], else (unset included) dflt.
+inline bool knob_off(const char* name) {
+  const char* e = knob(name);
+  return e && e[0] == '0';
+}
+inline bool knob_on(const char* name) {
+  const char* e = knob(name);
+  return e && e[0] == '1';
+}
+inline int knob_int(const char* name, int lo, int hi, int dflt) {
+  const char* e = knob(name);
+  const int x = e ? atoi(e) : dflt;
+  return e && x >= lo && x <= hi ? x : dflt;
+}
 
 inline hipStream_t as_stream(void* s) { return reinterpret_cast<hipStream_t>(s); }
 

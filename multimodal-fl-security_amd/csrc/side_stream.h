@@ -72,14 +72,12 @@ struct AuxStream {
 inline bool aux_enabled(AuxKind kind) {
   if (kind == AUX_OPT) {
 #ifdef FLR_ABLATION
-    const char* e = flr::knob("FLR_SGD_OVERLAP");
-    return e && e[0] == '1';
+    return flr::knob_on("FLR_SGD_OVERLAP");
 #else
     return false;
 #endif
   }
-  const char* e = flr::knob(kind == AUX_TEXT ? "FLR_TEXT_STREAM" : "FLR_WGRAD_STREAM");
-  return !(e && e[0] == '0');
+  return !flr::knob_off(kind == AUX_TEXT ? "FLR_TEXT_STREAM" : "FLR_WGRAD_STREAM");
 }
 
 // The current device's stream of one kind; created on first use when create is

@@ -426,8 +426,7 @@ using namespace flr::conv;
 // FLR_CONV_GENERIC=1 forces the generic gathers (A/B timing and cross-checks).
 static int generic_conv_forced() {
   static const int v = [] {
-    const char* e = flr::knob("FLR_CONV_GENERIC");
-    return (e && e[0] == '1') ? 1 : 0;
+    return flr::knob_on("FLR_CONV_GENERIC") ? 1 : 0;
   }();
   return v;
 }

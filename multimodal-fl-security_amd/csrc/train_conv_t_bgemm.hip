@@ -1,6 +1,6 @@
 // Tap-major GEMM engine, unit 5 of 5: the batched dense GEMM (BGemm plans)
 // and the row sums.
-#include "conv_t_kernels.h"
+#include "conv_t_launch.h"
 
 using namespace flr;
 
@@ -12,24 +12,11 @@ int bgemm_mode(const float* p, int64_t s_k, int64_t s_row, int64_t s_r, int64_t 
   if (s_row == 1 && al && s_r % 4 == 0 && rows % 4 == 0) return convt::BM_KR;
   return convt::BM_G;
 }
-// Workgroup tile of the batched GEMM: 128 x 128 (each wave 64 x 64, its
-// fragments and bf16 splits reused twice) for the encoder-sized products
-// (M, N >= 128 and a long reduction or many outputs), 64 x 64 for the small
-// ones (the GRU recurrence and the head, M = batch = 32).  Partial edge tiles
-// are bounds-checked in the loads and stores.  FLR_BGEMM_TILE=11|22 forces it.
-inline int bgemm_tile(int M, int N, int R) {
-  const char* e = flr::knob("FLR_BGEMM_TILE");
-  const int forced = e ? atoi(e) : 0;
-  if (forced == 11 || forced == 22) return forced;
-  return (M >= 128 && N >= 128 && (R >= 256 || (int64_t)M * N >= 128 * 512)) ? 22 : 11;
-}
 template <int AM, int BMD>
 int bgemm_run(const convt::BGemmArgs& args, void* ws, size_t ws_bytes, hipStream_t st) {
   convt::BGemm<AM, BMD> pl;
   static_cast<convt::BGemmArgs&>(pl) = args;
-  if (bgemm_tile(args.m, args.n, args.r) == 22)
-    return convt::launch_tiles<convt::BGemm<AM, BMD>, 2, 2>(pl, ws, ws_bytes, st, "batched gemm");
-  return convt::launch_tiles<convt::BGemm<AM, BMD>, 1, 1>(pl, ws, ws_bytes, st, "batched gemm");
+  return convt::launch(pl, ws, ws_bytes, st, "batched gemm");
 }
 template <int AM>
 int bgemm_b(int bm, const convt::BGemmArgs& args, void* ws, size_t wsb, hipStream_t st) {
@@ -43,13 +30,13 @@ int bgemm_b(int bm, const convt::BGemmArgs& args, void* ws, size_t wsb, hipStrea
 
 extern "C" size_t flr_bgemm_workspace(int64_t batch, int64_t M, int64_t N, int64_t R) {
   if (batch < 1 || M < 1 || N < 1 || R < 0 || M > INT32_MAX || N > INT32_MAX || R > INT32_MAX) return 0;
-  // the larger of the two tile shapes' split counts (sub-tile count 1 or 4)
-  const int S = std::max(convt::choose_splits((int)M, (int)N, (int)R, (int)batch, 1, convt::bgemm_min_kt()),
-                         convt::choose_splits((int)M, (int)N, (int)R, (int)batch, 4, convt::bgemm_min_kt()));
-  size_t n = S > 1 ? (size_t)S * batch * M * N * sizeof(float) : 0;
+  convt::BGemm<convt::BM_G, convt::BM_G> pl;  // sizes only: the operand modes do not enter
+  pl.m = (int)M; pl.n = (int)N; pl.r = (int)R;
+  // either tile shape's split count (sub-tile count 1 or 4)
+  size_t n = convt::splits_bytes(pl.m, pl.n, pl.r, batch, convt::plan_min_kt(pl));
 #ifdef FLR_ABLATION
   // the pre-split form's bf16 planes of both operands (128 x 128 tiles), before the partials
-  if (convt::bgemm_presplit() && bgemm_tile((int)M, (int)N, (int)R) == 22)
+  if (convt::bgemm_presplit() && convt::plan_tile(pl) == 22)
     n += (convt::ps_plane_bytes(batch, M, R) + 255) / 256 * 256 + (convt::ps_plane_bytes(batch, N, R) + 255) / 256 * 256;
 #endif
   return n;

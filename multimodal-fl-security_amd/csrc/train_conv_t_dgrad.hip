@@ -74,10 +74,10 @@ extern "C" int flr_conv2d_bwd_data_t_sc(const float* dy, const float* w_t, int64
     convt::DgradFusedArgs fa;
     for (int c = 0; c < convt::FD_CLASSES; ++c) {
       fa.cls[c] = cls[c];
-      fa.S[c] = convt::dgrad_class_splits(cls[c], ws, ws_bytes);
+      fa.S[c] = convt::resolve(cls[c], ws, ws_bytes).S;
     }
     fa.sc = sc ? scls[0] : cls[0];
-    fa.Ssc = sc ? convt::dgrad_class_splits(scls[0], ws, ws_bytes) : 0;
+    fa.Ssc = sc ? convt::resolve(scls[0], ws, ws_bytes).S : 0;
     return convt::launch_dgrad_fused(fa, as_stream(stream), "conv bwd data (tap-major, fused classes)");
   }
   rc = dgrad_per_class(cls, nc, ws, ws_bytes, stream);
@@ -119,5 +119,5 @@ extern "C" int flr_conv2d_dgrad_class_splits(int64_t K, int64_t B, int64_t Cin, 
   const int nc = query_classes(K, B, Cin, H, W, Cout, KH, KW, stride, pad, g, cls);
   if (cls_index < 0 || cls_index >= nc) return 0;
   // any non-null workspace pointer: only its size enters the choice
-  return convt::dgrad_class_splits(cls[cls_index], ws_bytes ? &g : nullptr, ws_bytes);
+  return convt::resolve(cls[cls_index], ws_bytes ? &g : nullptr, ws_bytes).S;
 }

@@ -1,5 +1,5 @@
 // Tap-major GEMM engine, unit 2 of 5: the convolution forward (FwdT).
-#include "conv_t_kernels.h"
+#include "conv_t_launch.h"
 
 using namespace flr;
 

@@ -1,7 +1,7 @@
 // Tap-major GEMM engine, unit 1 of 5: the explicit / gathered im2col path of
 // the short-reduction convolutions (the stem; Dense* and Stem* plans) and the
 // tap-major workspace query.
-#include "conv_t_kernels.h"
+#include "conv_t_launch.h"
 
 namespace flr {
 namespace convt {

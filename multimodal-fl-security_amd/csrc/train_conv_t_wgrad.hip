@@ -1,6 +1,6 @@
 // Tap-major GEMM engine, unit 4 of 5: the weight gradient (WgtT) with its
 // clip-norm partials, the dead-tap zero fill and the resident form's probe.
-#include "conv_t_kernels.h"
+#include "conv_t_launch.h"
 
 namespace flr {
 namespace convt {
@@ -33,7 +33,7 @@ extern "C" int64_t flr_conv2d_bwd_weight_t_sq_slots(int64_t K, int64_t B, int64_
   if (!convt::args_ok(K, B, Cin, H, W, Cout, KH, KW, stride, pad)) return -1;
   convt::WgtT<true> pl;  // the slot count does not depend on the B-operand load form
   pl.g = conv::make_geom(K, B, Cin, H, W, Cout, KH, KW, stride, pad);
-  return pl.R() == 0 ? 0 : convt::sq_slots(pl);
+  return convt::sq_slots(pl);
 }
 
 extern "C" int flr_conv2d_wgrad_resident_ok(int64_t K, int64_t B, int64_t Cin, int64_t H, int64_t W, int64_t Cout,

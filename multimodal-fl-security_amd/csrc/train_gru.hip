@@ -803,8 +803,7 @@ __global__ __launch_bounds__(THREADS) void zero_h0_kernel(float* __restrict__ hs
 
 // FLR_GRU_SEQ=0 (read per call) turns the one-launch form off
 inline bool seq_shape_ok(int64_t K, int64_t B, int64_t T, int64_t H) {
-  const char* e = flr::knob("FLR_GRU_SEQ");
-  if (e && e[0] == '0') return false;
+  if (flr::knob_off("FLR_GRU_SEQ")) return false;
   // byte offsets within a client's arrays (32 tile rows, 4 H the widest row) stay below 2 GB
   return B <= 32 && H % 32 == 0 && H <= SEQ_HMAX && 32 * (T + 1) * 4 * H < (int64_t)1 << 29;
 }
@@ -930,8 +929,7 @@ extern "C" int flr_gru_seq_supported(int64_t K, int64_t B, int64_t T, int64_t H)
 // fourth round on.  FLR_GRU_SEQ=1 takes it at every eligible shape.
 extern "C" int flr_gru_seq_preferred(int64_t K, int64_t B, int64_t T, int64_t H) {
   if (!flr_gru_seq_supported(K, B, T, H)) return 0;
-  const char* e = flr::knob("FLR_GRU_SEQ");
-  return (e && e[0] == '1') || K * (H / 32) > 3 * 256 ? 1 : 0;
+  return flr::knob_on("FLR_GRU_SEQ") || K * (H / 32) > 3 * 256 ? 1 : 0;
 }
 
 extern "C" int flr_gru_zero_h0(float* hseq, int64_t K, int64_t B, int64_t T, int64_t H, void* stream) {
