@@ -81,20 +81,15 @@ __global__ __launch_bounds__(THREADS, 2) void dsgemm_kernel(const Plan pl, int S
       for (int i = 0; i < MSW; ++i) {
         float v[8];
         frag(ia, MA{}, 64 * i + 32 * wm + l32, s, v);
-        split3(v, fa[i][0], fa[i][1], fa[i][2]);
+        split3_dot2(v, fa[i][0], fa[i][1], fa[i][2]);
       }
 #pragma unroll
       for (int j = 0; j < NS; ++j) {
         float v[8];
         frag(ib, MB{}, 64 * j + 32 * wn + l32, s, v);
-        split3(v, fb[j][0], fb[j][1], fb[j][2]);
+        split3_dot2(v, fb[j][0], fb[j][1], fb[j][2]);
       }
-#define FLR_DX(TA, TB)                                                                              \
-  _Pragma("unroll") for (int i = 0; i < MSW; ++i) _Pragma("unroll") for (int j = 0; j < NS; ++j) \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][TA], fb[j][TB], acc[i][j], 0, 0, 0);
-      // product-major, small terms first: sgemm_body's order
-      FLR_DX(1, 1) FLR_DX(0, 2) FLR_DX(2, 0) FLR_DX(0, 1) FLR_DX(1, 0) FLR_DX(0, 0)
-#undef FLR_DX
+      mfma6_blocks<MSW, NS>(acc, fa, fb);
     }
   };
   const int ntile = rend > rbeg ? (rend - rbeg + BK - 1) / BK : 0;
@@ -120,7 +115,7 @@ __global__ __launch_bounds__(THREADS, 2) void dsgemm_kernel(const Plan pl, int S
 inline bool bgemm_dma() { return knob_on("FLR_BGEMM_DMA"); }
 // ---- the pre-split form (batched GEMMs with 128 x 128 tiles, FLR_BGEMM_PRESPLIT=1; measured slower) --
 // Each operand is split into bf16 hi / mid / lo ONCE per GEMM by presplit_kernel
-// (the same split3 as every other form) into k-contiguous planes in the
+// (the same split3_dot2 as every other form) into k-contiguous planes in the
 // workspace, [3][K][rows_pad][R_pad] with rows padded to 128 and R to 32 by
 // zeros.  The GEMM (psgemm_kernel) is then a plain six-product bf16 loop: each
 // 16-deep k-step's three A and three B planes go global -> LDS by
@@ -177,7 +172,7 @@ __global__ __launch_bounds__(THREADS) void presplit_kernel(const float* __restri
       }
     }
     bf16x8 t0, t1, t2;
-    split3(v, t0, t1, t2);
+    split3_dot2(v, t0, t1, t2);
     const int64_t plane = (int64_t)K * rows_pad * R_pad;
     const int64_t o = ((int64_t)k * rows_pad + row) * R_pad + 8 * grp;
     *reinterpret_cast<bf16x8*>(planes + o) = t0;
@@ -264,11 +259,7 @@ __global__ __launch_bounds__(THREADS, 2) void psgemm_kernel(const Plan pl, int S
       for (int j = 0; j < NS; ++j)
 #pragma unroll
         for (int t = 0; t < 3; ++t) fb[j][t] = frag(sg, 1, t, 64 * j + 32 * wn + l32);
-#define FLR_PX(TA, TB)                                                                              \
-  _Pragma("unroll") for (int i = 0; i < MSW; ++i) _Pragma("unroll") for (int j = 0; j < NS; ++j) \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][TA], fb[j][TB], acc[i][j], 0, 0, 0);
-      FLR_PX(1, 1) FLR_PX(0, 2) FLR_PX(2, 0) FLR_PX(0, 1) FLR_PX(1, 0) FLR_PX(0, 0)
-#undef FLR_PX
+      mfma6_blocks<MSW, NS>(acc, fa, fb);
     }
   }
   store_tiles<Plan, MSW, NS>(pl, S, part, k, split, m0, n0, h, l32, M, N, acc, sub_tiles<MSW, NS>(wm, wn));

@@ -68,9 +68,9 @@ __device__ __forceinline__ void fd_ksum(const DgradT& pl, int S, int k, int m0, 
   };
   auto split_all = [&]() {
 #pragma unroll
-    for (int i = 0; i < MS; ++i) split3(ra[i], pa[i][0], pa[i][1], pa[i][2]);
+    for (int i = 0; i < MS; ++i) split3_dot2(ra[i], pa[i][0], pa[i][1], pa[i][2]);
 #pragma unroll
-    for (int j = 0; j < NS; ++j) split3(rb[j], pb[j][0], pb[j][1], pb[j][2]);
+    for (int j = 0; j < NS; ++j) split3_dot2(rb[j], pb[j][0], pb[j][1], pb[j][2]);
   };
   auto write_all = [&]() {
 #pragma unroll
@@ -100,15 +100,8 @@ __device__ __forceinline__ void fd_ksum(const DgradT& pl, int S, int k, int m0, 
           fb[s][j][q] = *reinterpret_cast<const bf16x8*>(&Ls[MS + j][q][zimg(b_row(), ko >> 3)]);
     }
     __builtin_amdgcn_sched_barrier(0);
-#define FLR_SX(TA, TB)                                                                              \
-  _Pragma("unroll") for (int i = 0; i < MSW; ++i) _Pragma("unroll") for (int j = 0; j < NS; ++j) \
-    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][i][TA], fb[s][j][TB], acc[i][j], 0, 0, 0);
 #pragma unroll
-    for (int s = 0; s < NKS; ++s) {
-      // sgemm_body's order: product-major, small terms first
-      FLR_SX(1, 1) FLR_SX(0, 2) FLR_SX(2, 0) FLR_SX(0, 1) FLR_SX(1, 0) FLR_SX(0, 0)
-    }
-#undef FLR_SX
+    for (int s = 0; s < NKS; ++s) mfma6_blocks<MSW, NS>(acc, fa[s], fb[s]);
   };
   for (int split = 0; split < S; ++split) {
     const int rbeg = (int)((int64_t)ktiles * split / S) * BK;
@@ -174,9 +167,8 @@ __global__ __launch_bounds__(THREADS, SG_OCC) void fdgrad_kernel(const DgradFuse
 #pragma unroll
   for (int j = 0; j < NS; ++j) {
     const int n = n0 + n_off(j) + l32;
-    const uint32_t bb = udiv(n, p0.d_hcwc), p = n - bb * p0.Hc * p0.Wc;
-    const uint32_t ihc = udiv(p, p0.d_wc), iwc = p - ihc * p0.Wc;
-    col[j] = n < N ? (int)(k * g.sxk + bb * g.sxb + 2 * ihc * g.W + 2 * iwc) : -1;
+    const DgradT::Col c = p0.col(n);
+    col[j] = n < N ? (int)(k * g.sxk + c.bb * g.sxb + 2 * c.ihc * g.W + 2 * c.iwc) : -1;
   }
   f32x16 run[MSW][NS];
   if (fa.Ssc > 0 && c0 == 0) {  // the shortcut's gradient first: it waits in the slab for class (0, 0)

@@ -223,6 +223,15 @@ __global__ __launch_bounds__(THREADS, 2) void tgemm_kernel(const Plan pl, int S,
 #pragma unroll
     for (int j = 0; j < NS; ++j) stash<Plan::LB>(Bs[buf][j], rb[j], tid);
   };
+  // The six products over the MS x NS blocks, product-major (bf16x6.h's order: mfma6_product<P>).
+  // The loops stay in the kernel body: inside a helper that takes the term arrays they compile to
+  // another register allocation (profiles/gemm_core/README.md).
+#define FLR_X6P(P, AH, AM, AL, BH, BM, BL)                                                        \
+  _Pragma("unroll") for (int i = 0; i < MS; ++i) _Pragma("unroll") for (int j = 0; j < NS; ++j) \
+      mfma6_product<P>(acc[i][j], AH[i], AM[i], AL[i], BH[j], BM[j], BL[j]);
+#define FLR_X6P_ALL(...)                                                                           \
+  FLR_X6P(0, __VA_ARGS__) FLR_X6P(1, __VA_ARGS__) FLR_X6P(2, __VA_ARGS__) FLR_X6P(3, __VA_ARGS__) \
+  FLR_X6P(4, __VA_ARGS__) FLR_X6P(5, __VA_ARGS__)
   if constexpr (X6 == 2) {
     // Software-pipelined bf16x6 loop (the default form).  A wave issues in
     // order, so its fragment reads, bf16 splits, LDS stash and global loads
@@ -248,13 +257,8 @@ __global__ __launch_bounds__(THREADS, 2) void tgemm_kernel(const Plan pl, int S,
         for (int j = 0; j < NS; ++j) frag8<Plan::LB>(Bs[buf][j], 32 * wn + l32, 16 * s + 8 * h, vb[j]);
       };
 #define FLR_SPLIT_ALL(AH, AM, AL, BH, BM, BL)                                       \
-  _Pragma("unroll") for (int i = 0; i < MS; ++i) split3(va[i], AH[i], AM[i], AL[i]); \
-  _Pragma("unroll") for (int j = 0; j < NS; ++j) split3(vb[j], BH[j], BM[j], BL[j]);
-#define FLR_X6P(AV, BV)                                                                           \
-  _Pragma("unroll") for (int i = 0; i < MS; ++i) _Pragma("unroll") for (int j = 0; j < NS; ++j) \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AV[i], BV[j], acc[i][j], 0, 0, 0);
-#define FLR_X6P_ALL(AH, AM, AL, BH, BM, BL) \
-  FLR_X6P(AM, BM) FLR_X6P(AH, BL) FLR_X6P(AL, BH) FLR_X6P(AH, BM) FLR_X6P(AM, BH) FLR_X6P(AH, BH)
+  _Pragma("unroll") for (int i = 0; i < MS; ++i) split3_dot2(va[i], AH[i], AM[i], AL[i]); \
+  _Pragma("unroll") for (int j = 0; j < NS; ++j) split3_dot2(vb[j], BH[j], BM[j], BL[j]);
       load(rbeg);
       stash_all(0);
       __syncthreads();
@@ -278,8 +282,6 @@ __global__ __launch_bounds__(THREADS, 2) void tgemm_kernel(const Plan pl, int S,
         cur ^= 1;
       }
 #undef FLR_SPLIT_ALL
-#undef FLR_X6P
-#undef FLR_X6P_ALL
     }
   } else {
   if (rbeg < rend) {
@@ -303,7 +305,7 @@ __global__ __launch_bounds__(THREADS, 2) void tgemm_kernel(const Plan pl, int S,
 #pragma unroll
             for (int q = 0; q < 8; ++q) ah[i][q] = am[i][q] = al[i][q] = (__bf16)v[q];
           } else {
-            split3(v, ah[i], am[i], al[i]);
+            split3_dot2(v, ah[i], am[i], al[i]);
           }
         }
 #pragma unroll
@@ -314,37 +316,17 @@ __global__ __launch_bounds__(THREADS, 2) void tgemm_kernel(const Plan pl, int S,
 #pragma unroll
             for (int q = 0; q < 8; ++q) bh[j][q] = bm[j][q] = bl[j][q] = (__bf16)v[q];
           } else {
-            split3(v, bh[j], bm[j], bl[j]);
+            split3_dot2(v, bh[j], bm[j], bl[j]);
           }
         }
         if (prio) __builtin_amdgcn_s_setprio(1);
         if constexpr (X6 >= 3) {
-          // product-major: the MS*NS accumulator chains interleave, so a chain's
-          // next MFMA never waits on its own previous one (small terms first)
-#define FLR_X6_STEP(AV, BV)                                                              \
-  _Pragma("unroll") for (int i = 0; i < MS; ++i) _Pragma("unroll") for (int j = 0; j < NS; ++j) \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AV[i], BV[j], acc[i][j], 0, 0, 0);
-          FLR_X6_STEP(am, bm)
-          FLR_X6_STEP(ah, bl)
-          FLR_X6_STEP(al, bh)
-          FLR_X6_STEP(ah, bm)
-          FLR_X6_STEP(am, bh)
-          FLR_X6_STEP(ah, bh)
-#undef FLR_X6_STEP
-        } else {
+          FLR_X6P_ALL(ah, am, al, bh, bm, bl)
+        } else {  // accumulator-chain order: each block's six products back to back
 #pragma unroll
           for (int i = 0; i < MS; ++i)
 #pragma unroll
-            for (int j = 0; j < NS; ++j) {  // small terms first
-              f32x16 c = acc[i][j];
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bm[j], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl[j], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh[j], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bm[j], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am[i], bh[j], c, 0, 0, 0);
-              c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh[j], c, 0, 0, 0);
-              acc[i][j] = c;
-            }
+            for (int j = 0; j < NS; ++j) acc[i][j] = mfma6(acc[i][j], ah[i], am[i], al[i], bh[j], bm[j], bl[j]);
         }
         if (prio) __builtin_amdgcn_s_setprio(0);
       }
@@ -373,6 +355,8 @@ __global__ __launch_bounds__(THREADS, 2) void tgemm_kernel(const Plan pl, int S,
     cur ^= 1;
   }
   }  // old loop (FLR_GEMM=f32 | chain | old | A)
+#undef FLR_X6P_ALL
+#undef FLR_X6P
   const TileOffs<MS, NS> off = sub_tiles<MS, NS>(wm, wn);
   store_tiles<Plan, MS, NS>(pl, S, part, k, split, m0, n0, h, l32, M, N, acc, off);
   if constexpr (has_sq<Plan>::value) {
@@ -489,9 +473,9 @@ __device__ __forceinline__ void sgemm_body(const Plan& pl, int S, float* __restr
   };
   auto split_all = [&]() {
 #pragma unroll
-    for (int i = 0; i < MS; ++i) split3(ra[i], pa[i][0], pa[i][1], pa[i][2]);
+    for (int i = 0; i < MS; ++i) split3_dot2(ra[i], pa[i][0], pa[i][1], pa[i][2]);
 #pragma unroll
-    for (int j = 0; j < NS; ++j) split3(rb[j], pb[j][0], pb[j][1], pb[j][2]);
+    for (int j = 0; j < NS; ++j) split3_dot2(rb[j], pb[j][0], pb[j][1], pb[j][2]);
   };
   auto write_all = [&]() {
 #pragma unroll
@@ -526,15 +510,8 @@ __device__ __forceinline__ void sgemm_body(const Plan& pl, int S, float* __restr
           fb[s][j][q] = *reinterpret_cast<const bf16x8*>(&Ls[MS + j][q][zimg(b_row(), ko >> 3)]);
     }
     __builtin_amdgcn_sched_barrier(0);  // the scheduler would sink the second k-step's reads again
-#define FLR_SX(TA, TB)                                                                              \
-  _Pragma("unroll") for (int i = 0; i < MSW; ++i) _Pragma("unroll") for (int j = 0; j < NS; ++j) \
-    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][i][TA], fb[s][j][TB], acc[i][j], 0, 0, 0);
 #pragma unroll
-    for (int s = 0; s < NKS; ++s) {
-      // product-major, small terms first (term 0 = hi, 1 = mid, 2 = lo)
-      FLR_SX(1, 1) FLR_SX(0, 2) FLR_SX(2, 0) FLR_SX(0, 1) FLR_SX(1, 0) FLR_SX(0, 0)
-    }
-#undef FLR_SX
+    for (int s = 0; s < NKS; ++s) mfma6_blocks<MSW, NS>(acc, fa[s], fb[s]);
   };
   const int ntile = rend > rbeg ? (rend - rbeg + BK - 1) / BK : 0;
   if (ntile > 0) {
@@ -642,7 +619,7 @@ __global__ __launch_bounds__(THREADS, SG_OCC) void rgemm_kernel(const Plan pl, i
 #pragma unroll
         for (int e = 0; e < 8; ++e) rbv[j][c][e] = ld1(rb, vb, (32 * c + e) * cs * 4);
     }
-    split3(ra, pa[0], pa[1], pa[2]);
+    split3_dot2(ra, pa[0], pa[1], pa[2]);
     write_a();
     pl.load_a8(sa, std::min(BK, rlast), ra);
 #pragma unroll
@@ -650,7 +627,7 @@ __global__ __launch_bounds__(THREADS, SG_OCC) void rgemm_kernel(const Plan pl, i
 #pragma unroll
       for (int c = 0; c < 2; ++c) {
         bf16x8 pb[3];
-        split3(rbv[j][c], pb[0], pb[1], pb[2]);
+        split3_dot2(rbv[j][c], pb[0], pb[1], pb[2]);
 #pragma unroll
         for (int t = 0; t < 3; ++t)
           *reinterpret_cast<bf16x8*>(&Lb[c][t][zimg(64 * j + (tid & 63), kc)]) = pb[t];
@@ -689,16 +666,9 @@ __global__ __launch_bounds__(THREADS, SG_OCC) void rgemm_kernel(const Plan pl, i
           fb[s][j][q] = *reinterpret_cast<const bf16x8*>(&Lb[c][q][zimg(brow[j], 2 * s + h)]);
     }
     __builtin_amdgcn_sched_barrier(0);
-#define FLR_SX(TA, TB)                              \
-  _Pragma("unroll") for (int j = 0; j < 2; ++j) \
-    acc[0][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[s][0][TA], fb[s][j][TB], acc[0][j], 0, 0, 0);
 #pragma unroll
-    for (int s = 0; s < NKS; ++s) {
-      // product-major, small terms first (term 0 = hi, 1 = mid, 2 = lo)
-      FLR_SX(1, 1) FLR_SX(0, 2) FLR_SX(2, 0) FLR_SX(0, 1) FLR_SX(1, 0) FLR_SX(0, 0)
-    }
-#undef FLR_SX
-    split3(ra, pa[0], pa[1], pa[2]);
+    for (int s = 0; s < NKS; ++s) mfma6_blocks<1, 2>(acc, fa[s], fb[s]);
+    split3_dot2(ra, pa[0], pa[1], pa[2]);
     __syncthreads();  // every wave's fragment reads of tile t are done
     write_a();
     pl.load_a8(sa, std::min((t + 2) * BK, rlast), ra);
@@ -817,9 +787,9 @@ __global__ __launch_bounds__(THREADS, SG_OCC) void wsgemm_kernel(const Plan pl, 
   };
   auto split_all = [&]() {
 #pragma unroll
-    for (int i = 0; i < MS; ++i) split3(ra[i], pa[i][0], pa[i][1], pa[i][2]);
+    for (int i = 0; i < MS; ++i) split3_dot2(ra[i], pa[i][0], pa[i][1], pa[i][2]);
 #pragma unroll
-    for (int j = 0; j < NS; ++j) split3(rb[j], pb[j][0], pb[j][1], pb[j][2]);
+    for (int j = 0; j < NS; ++j) split3_dot2(rb[j], pb[j][0], pb[j][1], pb[j][2]);
   };
   auto write_all = [&]() {
 #pragma unroll
@@ -859,12 +829,7 @@ __global__ __launch_bounds__(THREADS, SG_OCC) void wsgemm_kernel(const Plan pl, 
             if constexpr (TB) fb[j][q] = tread(Lt[MS + j][q], rb_off, s);
             else fb[j][q] = *reinterpret_cast<const bf16x8*>(&Lt[MS + j][q][zimg(32 * wn + l32, 2 * s + h)]);
           }
-#define FLR_SX(TA, TB)                                                                              \
-  _Pragma("unroll") for (int i = 0; i < MS; ++i) _Pragma("unroll") for (int j = 0; j < NS; ++j) \
-      acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i][TA], fb[j][TB], acc[i][j], 0, 0, 0);
-        // product-major, small terms first (term 0 = hi, 1 = mid, 2 = lo)
-        FLR_SX(1, 1) FLR_SX(0, 2) FLR_SX(2, 0) FLR_SX(0, 1) FLR_SX(1, 0) FLR_SX(0, 0)
-#undef FLR_SX
+        mfma6_blocks<MS, NS>(acc, fa, fb);
       }
   };
   const int ntile = rend > rbeg ? (rend - rbeg + BK - 1) / BK : 0;
@@ -977,8 +942,8 @@ __global__ __launch_bounds__(THREADS, 3) void rwgemm_kernel(const Plan pl, int S
   auto split_all = [&]() {
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      split3(rxv[c], px[c][0], px[c][1], px[c][2]);
-      split3(ryv[c], py[c][0], py[c][1], py[c][2]);
+      split3_dot2(rxv[c], px[c][0], px[c][1], px[c][2]);
+      split3_dot2(ryv[c], py[c][0], py[c][1], py[c][2]);
     }
   };
   auto write_all = [&]() {
@@ -1059,15 +1024,7 @@ __global__ __launch_bounds__(THREADS, 3) void rwgemm_kernel(const Plan pl, int S
           const int o0 = (int)(xoff[t][ks] & 0xffffu), o1 = (int)(xoff[t][ks] >> 16);
 #pragma unroll
           for (int q = 0; q < 3; ++q) fx[q] = tread(Lx[q], o0, o1);
-          f32x16 c = acc[t][0][0];
-          // small terms first (term 0 = hi, 1 = mid, 2 = lo)
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fx[1], fy[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fx[0], fy[2], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fx[2], fy[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fx[0], fy[1], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fx[1], fy[0], c, 0, 0, 0);
-          c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fx[0], fy[0], c, 0, 0, 0);
-          acc[t][0][0] = c;
+          acc[t][0][0] = mfma6(acc[t][0][0], fx, fy);
         }
       }
     }

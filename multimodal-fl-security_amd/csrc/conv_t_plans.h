@@ -21,6 +21,15 @@ struct FwdT {  // y = conv(x, W_t): M = Cout, N = B*Ho*Wo, R = ntaps*Cin
   __host__ __device__ __forceinline__ int M() const { return g.Cout; }
   __host__ __device__ __forceinline__ int N() const { return g.B * g.Ho * g.Wo; }
   __host__ __device__ __forceinline__ int R() const { return g.ntaps * g.Cin; }
+  // column n of the GEMM -> (image, output row, output column)
+  struct Col {
+    uint32_t bb, oh, ow;
+  };
+  __device__ __forceinline__ Col col(int n) const {
+    const uint32_t bb = udiv(n, g.d_howo), p = n - bb * g.Ho * g.Wo;
+    const uint32_t oh = udiv(p, g.d_wo), ow = p - oh * g.Wo;
+    return Col{bb, oh, ow};
+  }
   struct State {
     rsrc_t ra, rb;
     unsigned a0;            // byte offset of (k-row tid/16, m 4*(tid%16)) at tap 0, ci 0
@@ -35,11 +44,10 @@ struct FwdT {  // y = conv(x, W_t): M = Cout, N = B*Ho*Wo, R = ntaps*Cin
     s.a0 = (unsigned)(((tid / 16) * g.Cout + m0 + 4 * (tid % 16)) * 4);
     const int n = n0 + tid % 64;
     s.nok = n < N();
-    const uint32_t bb = udiv(n, g.d_howo), p = n - bb * g.Ho * g.Wo;
-    const uint32_t oh = udiv(p, g.d_wo), ow = p - oh * g.Wo;
-    s.ih0 = (int)oh * g.stride - g.pad;
-    s.iw0 = (int)ow * g.stride - g.pad;
-    s.xoff = (int)(bb * g.sxb + (tid / 64) * g.sxc);
+    const Col c = col(n);
+    s.ih0 = (int)c.oh * g.stride - g.pad;
+    s.iw0 = (int)c.ow * g.stride - g.pad;
+    s.xoff = (int)(c.bb * g.sxb + (tid / 64) * g.sxc);
     return s;
   }
   __device__ __forceinline__ void load_a(const State& s, int r0, float (&a)[8]) const {
@@ -80,12 +88,7 @@ struct FwdT {  // y = conv(x, W_t): M = Cout, N = B*Ho*Wo, R = ntaps*Cin
   __device__ __forceinline__ int64_t ldm() const { return g.syc; }
   // ---- k-contiguous loads for the split-at-stash kernel: thread (row = tid & 63,
   // k = 8 (tid >> 6) .. +7) of a 64 x 32 sub-tile
-  struct State8 {
-    rsrc_t ra, rb;
-    unsigned a0;
-    int ih0, iw0, xoff;
-    bool nok;
-  };
+  using State8 = State;  // the same fields, filled for the k-contiguous mapping
   __device__ __forceinline__ State8 init8(int k, int m0, int n0, int tid) const {
     State8 s;
     const int KK = g.KH * g.KW;
@@ -95,11 +98,10 @@ struct FwdT {  // y = conv(x, W_t): M = Cout, N = B*Ho*Wo, R = ntaps*Cin
     s.a0 = (unsigned)((k0 * g.Cout + m0 + row) * 4);
     const int n = n0 + row;
     s.nok = n < N();
-    const uint32_t bb = udiv(n, g.d_howo), p = n - bb * g.Ho * g.Wo;
-    const uint32_t oh = udiv(p, g.d_wo), ow = p - oh * g.Wo;
-    s.ih0 = (int)oh * g.stride - g.pad;
-    s.iw0 = (int)ow * g.stride - g.pad;
-    s.xoff = (int)(bb * g.sxb + k0 * g.sxc);
+    const Col c = col(n);
+    s.ih0 = (int)c.oh * g.stride - g.pad;
+    s.iw0 = (int)c.ow * g.stride - g.pad;
+    s.xoff = (int)(c.bb * g.sxb + k0 * g.sxc);
     return s;
   }
   __device__ __forceinline__ void load_a8(const State8& s, int r0, float (&a)[8]) const {  // A(co, ci): lanes along co
@@ -133,11 +135,10 @@ struct FwdT {  // y = conv(x, W_t): M = Cout, N = B*Ho*Wo, R = ntaps*Cin
   __device__ __forceinline__ rsrc_t res_rsrc(int k) const { return make_rsrc(x + k * g.sxk, g.xext); }
   __device__ __forceinline__ int res_cs() const { return (int)g.sxc; }
   __device__ __forceinline__ int res_col(int n, int& oh, int& ow) const {
-    const uint32_t bb = udiv(n, g.d_howo), p = n - bb * g.Ho * g.Wo;
-    const uint32_t h = udiv(p, g.d_wo);
-    oh = (int)h;
-    ow = (int)(p - h * g.Wo);
-    return (int)(bb * g.sxb) + oh * g.W + ow;
+    const Col c = col(n);
+    oh = (int)c.oh;
+    ow = (int)c.ow;
+    return (int)(c.bb * g.sxb) + oh * g.W + ow;
   }
   __device__ __forceinline__ void res_shift(int slot, int& dh, int& dw) const {
     int kh, kw;
@@ -169,6 +170,15 @@ struct DgradT {
   __host__ __device__ __forceinline__ int M() const { return g.Cin; }
   __host__ __device__ __forceinline__ int N() const { return g.B * Hc * Wc; }
   __host__ __device__ __forceinline__ int R() const { return ntc * g.Cout; }
+  // column n of the class's GEMM -> (image, row, column) in the class's Hc x Wc grid
+  struct Col {
+    uint32_t bb, ihc, iwc;
+  };
+  __device__ __forceinline__ Col col(int n) const {
+    const uint32_t bb = udiv(n, d_hcwc), p = n - bb * Hc * Wc;
+    const uint32_t ihc = udiv(p, d_wc), iwc = p - ihc * Wc;
+    return Col{bb, ihc, iwc};
+  }
   struct State {
     rsrc_t ra, rb;
     unsigned a0;
@@ -183,11 +193,10 @@ struct DgradT {
     s.a0 = (unsigned)(((m0 + tid / 8) * g.Cout + 4 * (tid % 8)) * 4);
     const int n = n0 + tid % 64;
     s.nok = n < N();
-    const uint32_t bb = udiv(n, d_hcwc), p = n - bb * Hc * Wc;
-    const uint32_t ihc = udiv(p, d_wc), iwc = p - ihc * Wc;
-    s.ih = ca + (int)ihc * g.stride + g.pad;
-    s.iw = cb + (int)iwc * g.stride + g.pad;
-    s.yoff = (int)(bb * g.syb + (tid / 64) * g.syc);
+    const Col c = col(n);
+    s.ih = ca + (int)c.ihc * g.stride + g.pad;
+    s.iw = cb + (int)c.iwc * g.stride + g.pad;
+    s.yoff = (int)(c.bb * g.syb + (tid / 64) * g.syc);
     return s;
   }
   __device__ __forceinline__ void load_a(const State& s, int r0, float (&a)[8]) const {
@@ -221,30 +230,21 @@ struct DgradT {
 #pragma unroll
     for (int i = 0; i < 8; ++i) b[i] = ld1(s.rb, vb, cb0 + i * 4 * cs * 4);
   }
-  __device__ __forceinline__ void store(int k, int m, int n, float v) const {
-    const uint32_t bb = udiv(n, d_hcwc), p = n - bb * Hc * Wc;
-    const uint32_t ihc = udiv(p, d_wc), iwc = p - ihc * Wc;
-    const int ih = ca + (int)ihc * g.stride, iw = cb + (int)iwc * g.stride;
-    const int64_t i = k * g.sxk + m * g.sxc + bb * g.sxb + ih * g.W + iw;
-    dx[i] = add ? __fadd_rn(v, add[i]) : v;
-  }
   __device__ __forceinline__ int64_t index(int k, int m, int n) const {  // dx offset of output (m, n) of client k
-    const uint32_t bb = udiv(n, d_hcwc), p = n - bb * Hc * Wc;
-    const uint32_t ihc = udiv(p, d_wc), iwc = p - ihc * Wc;
-    const int ih = ca + (int)ihc * g.stride, iw = cb + (int)iwc * g.stride;
-    return k * g.sxk + m * g.sxc + bb * g.sxb + ih * g.W + iw;
+    const Col c = col(n);
+    const int ih = ca + (int)c.ihc * g.stride, iw = cb + (int)c.iwc * g.stride;
+    return k * g.sxk + m * g.sxc + c.bb * g.sxb + ih * g.W + iw;
+  }
+  __device__ __forceinline__ void store(int k, int m, int n, float v) const {
+    const int64_t i = index(k, m, n);
+    dx[i] = add ? __fadd_rn(v, add[i]) : v;
   }
   // stride 1 (the one class is every pixel): dx[k][m][n] is linear in n
   __device__ __forceinline__ bool linear() const { return g.stride == 1; }
   __device__ __forceinline__ float* out() const { return dx; }
   __device__ __forceinline__ int64_t tile_base(int k, int m0, int n0) const { return k * g.sxk + m0 * g.sxc + n0; }
   __device__ __forceinline__ int64_t ldm() const { return g.sxc; }
-  struct State8 {
-    rsrc_t ra, rb;
-    unsigned a0;
-    int ih, iw, yoff;
-    bool nok;
-  };
+  using State8 = State;  // the same fields, filled for the k-contiguous mapping
   __device__ __forceinline__ State8 init8(int k, int m0, int n0, int tid) const {
     State8 s;
     const int KK = g.KH * g.KW;
@@ -255,11 +255,10 @@ struct DgradT {
     s.a0 = (unsigned)(((m0 + stash_row<QUAD_A>(tid)) * g.Cout + stash_k<QUAD_A>(tid)) * 4);
     const int n = n0 + row;
     s.nok = n < N();
-    const uint32_t bb = udiv(n, d_hcwc), p = n - bb * Hc * Wc;
-    const uint32_t ihc = udiv(p, d_wc), iwc = p - ihc * Wc;
-    s.ih = ca + (int)ihc * g.stride + g.pad;
-    s.iw = cb + (int)iwc * g.stride + g.pad;
-    s.yoff = (int)(bb * g.syb + k0 * g.syc);
+    const Col c = col(n);
+    s.ih = ca + (int)c.ihc * g.stride + g.pad;
+    s.iw = cb + (int)c.iwc * g.stride + g.pad;
+    s.yoff = (int)(c.bb * g.syb + k0 * g.syc);
     return s;
   }
   __device__ __forceinline__ void load_a8(const State8& s, int r0, float (&a)[8]) const {  // A(ci, co): 8 consecutive co
@@ -296,11 +295,10 @@ struct DgradT {
   __device__ __forceinline__ rsrc_t res_rsrc(int k) const { return make_rsrc(dy + k * g.syk, g.yext); }
   __device__ __forceinline__ int res_cs() const { return (int)g.syc; }
   __device__ __forceinline__ int res_col(int n, int& oh, int& ow) const {
-    const uint32_t bb = udiv(n, d_hcwc), p = n - bb * Hc * Wc;
-    const uint32_t h = udiv(p, d_wc);
-    oh = (int)h;
-    ow = (int)(p - h * Wc);
-    return (int)(bb * g.syb) + oh * g.Wo + ow;
+    const Col c = col(n);
+    oh = (int)c.ihc;
+    ow = (int)c.iwc;
+    return (int)(c.bb * g.syb) + oh * g.Wo + ow;
   }
   __device__ __forceinline__ void res_shift(int slot, int& dh, int& dw) const {
     int kh, kw;

@@ -25,16 +25,20 @@
 // buffered LDS, deterministic split-K for long reductions (partials reduced
 // in split order).
 //
-// The code lives in five headers and five translation units:
-//   conv_t_prims.h     (this file) buffer loads, fp32 LDS images, the bf16 split, knobs
+// The code lives in seven headers and five translation units:
+//   bf16x6.h           buffer loads, the bf16 split, the six-product order (shared
+//                      with train_gru.hip and train_stem.hip)
+//   conv_t_prims.h     (this file) tile constants, fp32 LDS images, knobs
 //   conv_t_plans.h     the load plans: FwdT, DgradT, WgtT, Dense*, Stem*, BGemm
 //   conv_t_kernels.h   the epilogue and the GEMM kernels
+//   conv_t_dgrad_fused.h  the fused strided data gradient (sgemm_body's K-loop per parity class)
 //   conv_t_launch.h    the launch policy (form, tile, split-K: resolve) and launch
 //   conv_t_ablation.h  the measured-slower and timing-only forms (make ABLATION=1 only)
 //   train_conv_t_{im2col,fwd,dgrad,wgrad,bgemm}.hip   the extern "C" entry points;
 //   each unit instantiates only the kernels its entry points launch.
 #pragma once
 
+#include "bf16x6.h"
 #include "conv_common.h"
 
 #include <algorithm>
@@ -47,34 +51,12 @@ namespace convt {
 using conv::Geom;
 using conv::udiv;
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 constexpr int BM = 64, BN = 64, BK = 32, THREADS = 256;
 constexpr int SKR = 68;  // [k][row] image row stride (floats)
 constexpr int SRK = 36;  // [row][k] image row stride
 constexpr int TILE = 64 * SRK;
-constexpr unsigned SENT = 0x80000000u;  // out-of-range voffset: the load returns 0
 
 enum Lay { KR_VEC = 0, KR_GATHER = 1, RK_VEC = 2, RK_GATHER = 3 };
-
-using rsrc_t = __amdgpu_buffer_rsrc_t;
-
-__device__ __forceinline__ rsrc_t make_rsrc(const float* p, int64_t nfloats) {
-  const uint64_t a = reinterpret_cast<uint64_t>(p);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-  const int bytes = __builtin_amdgcn_readfirstlane((int)(nfloats * 4));
-  void* b = reinterpret_cast<void*>(((uint64_t)hi << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(b, (short)0, bytes, 0x00020000);
-}
-__device__ __forceinline__ float ld1(rsrc_t r, unsigned voff, int soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, voff, soff, 0));
-}
-__device__ __forceinline__ f32x4 ld4(rsrc_t r, unsigned voff, int soff) {
-  return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0));
-}
 
 // ---- LDS images -------------------------------------------------------------
 template <int LAY>
@@ -109,17 +91,9 @@ __device__ __forceinline__ f32x4 frag(const float* buf, int rb, int j, int h) {
   }
 }
 
-// ---- the bf16x6 MFMA form ----------------------------------------------------
-// f32 MFMA runs at 1/16 of the bf16 rate on gfx950.  Each f32 operand is split
-// into three round-to-nearest bf16 terms, x = hi + mid + lo (the residual is
-// below 2^-24 |x|: 24 significand bits in three 8-bit pieces), and the six
-// products whose order is above 2^-24 (hi*hi, hi*mid, mid*hi, mid*mid, hi*lo,
-// lo*hi; every bf16 x bf16 product is exact in the fp32 accumulator) run on
-// v_mfma_f32_32x32x16_bf16: 6 x 32 cycles per 16-deep k-step against 8 x 64 for
-// v_mfma_f32_32x32x2_f32, at a per-product error of a few 2^-24 |a b| — the
-// rounding of an fp32 product.  The LDS images stay fp32; each wave splits
-// the eight values of its fragment: lane (l32, h) supplies row l32 and
-// reduction indices k0 .. k0+7, k0 = 16 s + 8 h.
+// ---- the bf16x6 MFMA form (bf16x6.h) on fp32 images ----------------------------
+// The LDS images stay fp32; each wave splits the eight values of its fragment:
+// lane (l32, h) supplies row l32 and reduction indices k0 .. k0+7, k0 = 16 s + 8 h.
 template <int LAY>
 __device__ __forceinline__ void frag8(const float* buf, int rb, int k0, float (&v)[8]) {
   if constexpr (LAY == RK_VEC || LAY == RK_GATHER) {
@@ -134,38 +108,6 @@ __device__ __forceinline__ void frag8(const float* buf, int rb, int k0, float (&
     const float* p = buf + k0 * SKR + rb;
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = p[e * SKR];
-  }
-}
-
-// The residuals r = v - (float)bf16(v) come from v_dot2_f32_bf16 against
-// (-1, 0) / (0, -1): one instruction per value instead of a bf16 -> fp32
-// expansion plus a subtraction.  r is exact either way (|r| <= half a bf16
-// ulp of v, representable in fp32), so the split is bit-identical to the
-// plain form, expansion + subtraction (tools/hip/split_check.hip holds both and
-// checks 2^24 random patterns).
-__device__ __forceinline__ void split3(const float (&v)[8], bf16x8& hi, bf16x8& mid, bf16x8& lo) {
-  typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-  // (-1, 0) and (0, -1) as opaque SGPRs: hipcc encodes a (-1, 0) constant as the
-  // inline constant -1.0, which the hardware reads as the fp32 bits, i.e. (0, -1)
-  unsigned klo, khi;  // non-volatile: the compiler may hoist / share them
-  asm("s_mov_b32 %0, 0xbf80" : "=s"(klo));
-  asm("s_mov_b32 %0, 0xbf800000" : "=s"(khi));
-  const bf16x2 nl = __builtin_bit_cast(bf16x2, klo), nh = __builtin_bit_cast(bf16x2, khi);
-#pragma unroll
-  for (int p = 0; p < 4; ++p) {
-    const float v0 = v[2 * p], v1 = v[2 * p + 1];
-    const bf16x2 a = {(__bf16)v0, (__bf16)v1};
-    const float r0 = __builtin_amdgcn_fdot2_f32_bf16(a, nl, v0, false);
-    const float r1 = __builtin_amdgcn_fdot2_f32_bf16(a, nh, v1, false);
-    const bf16x2 b = {(__bf16)r0, (__bf16)r1};
-    const float s0 = __builtin_amdgcn_fdot2_f32_bf16(b, nl, r0, false);
-    const float s1 = __builtin_amdgcn_fdot2_f32_bf16(b, nh, r1, false);
-    hi[2 * p] = a[0];
-    hi[2 * p + 1] = a[1];
-    mid[2 * p] = b[0];
-    mid[2 * p + 1] = b[1];
-    lo[2 * p] = (__bf16)s0;
-    lo[2 * p + 1] = (__bf16)s1;
   }
 }
 

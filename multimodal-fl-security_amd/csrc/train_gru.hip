@@ -19,7 +19,7 @@
 //   gates [K][T][B][4][H] r, z, n, h_n saved for backward
 //   dgh   [K][T][B][3H]   d(h W_hh^T + b_hh) per step, for dW_hh / db_hh
 //   dgi   [K][B][T][3H]   d(gi)
-#include "flr_common.h"
+#include "bf16x6.h"
 
 #include <stdlib.h>
 #include <string.h>
@@ -136,42 +136,10 @@ __global__ __launch_bounds__(THREADS) void bwd_step_kernel(const float* __restri
 // GEMM: per-product error a few 2^-24 |a b|).  The forward reads W_hh rows
 // ([3H][H], k-contiguous); the backward reads W_hh^T ([H][3H], transposed once
 // per optimizer step by flr_gru_transpose) so both operands load k-contiguous.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ void split1(float v, __bf16& hi, __bf16& mid, __bf16& lo) {
-  hi = (__bf16)v;
-  const float r1 = v - (float)hi;
-  mid = (__bf16)r1;
-  lo = (__bf16)(r1 - (float)mid);
-}
-
-__device__ __forceinline__ void split3(const float (&v)[8], bf16x8& hi, bf16x8& mid, bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    __bf16 a, b, c;
-    split1(v[j], a, b, c);
-    hi[j] = a;
-    mid[j] = b;
-    lo[j] = c;
-  }
-}
-
-// Raw buffer loads: an out-of-range byte offset returns 0 with no branch, so a
-// wave's loads of several k-steps stay in flight together (a per-lane branch
-// would join through register moves that wait on each load).
-using rsrc_t = __amdgpu_buffer_rsrc_t;
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr unsigned SENT = 0x80000000u;  // past every buffer here (< 2 GB)
-
-__device__ __forceinline__ rsrc_t make_rsrc(const float* p, int64_t nfloats) {
-  const uint64_t a = reinterpret_cast<uint64_t>(p);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-  const int bytes = __builtin_amdgcn_readfirstlane((int)(nfloats * 4));
-  void* base = reinterpret_cast<void*>(((uint64_t)hi << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(base, (short)0, bytes, 0x00020000);
-}
+// The split (split3_sub), the product order (mfma6) and the raw buffer loads are
+// bf16x6.h's: an out-of-range byte offset returns 0 with no branch, so a wave's
+// loads of several k-steps stay in flight together (a per-lane branch would join
+// through register moves that wait on each load).
 
 // 8 floats of a row starting at k0; zeros for an invalid row or past R.  V8: R
 // and k0 are multiples of 8, so k0 < R covers all 8.
@@ -202,17 +170,6 @@ __device__ __forceinline__ void pload8(rsrc_t r, bool in, int blk, int S, int s,
   const f32x4 y = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, off + 1024u, 0, 0));
   v[0] = x[0]; v[1] = x[1]; v[2] = x[2]; v[3] = x[3];
   v[4] = y[0]; v[5] = y[1]; v[6] = y[2]; v[7] = y[3];
-}
-
-__device__ __forceinline__ f32x16 mfma6(const bf16x8& ah, const bf16x8& am, const bf16x8& al, const bf16x8& bh,
-                                        const bf16x8& bm, const bf16x8& bl, f32x16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, c, 0, 0, 0);  // small terms first
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
-  return c;
 }
 
 // Workgroup -> (client, 32-unit block).  Workgroups go round-robin over the 8
@@ -300,12 +257,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SEQ ? 4
 #pragma unroll
     for (int q = 0; q < G; ++q) {
       bf16x8 ah, am, al;
-      split3(a[q], ah, am, al);
+      split3_sub(a[q], ah, am, al);
 #pragma unroll
       for (int g = 0; g < 3; ++g) {
         bf16x8 bh, bm, bl;
-        split3(b[q][g], bh, bm, bl);
-        acc[g] = mfma6(ah, am, al, bh, bm, bl, acc[g]);
+        split3_sub(b[q][g], bh, bm, bl);
+        acc[g] = mfma6(acc[g], ah, am, al, bh, bm, bl);
       }
     }
   }
@@ -410,9 +367,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(SEQ ? 6
 #pragma unroll
     for (int q = 0; q < G; ++q) {
       bf16x8 ah, am, al, bh, bm, bl;
-      split3(a[q], ah, am, al);
-      split3(b[q], bh, bm, bl);
-      acc = mfma6(ah, am, al, bh, bm, bl, acc);
+      split3_sub(a[q], ah, am, al);
+      split3_sub(b[q], bh, bm, bl);
+      acc = mfma6(acc, ah, am, al, bh, bm, bl);
     }
   }
   if constexpr (SEQ) {
@@ -564,8 +521,8 @@ __device__ __forceinline__ void wmma(const __bf16* a, const WBuf<G>& v, f32x16 (
 #pragma unroll
       for (int g = 0; g < G::NG; ++g) {
         bf16x8 bh, bm, bl;
-        split3(v[q][g], bh, bm, bl);
-        p[g] = mfma6(ah, am, al, bh, bm, bl, p[g]);
+        split3_sub(v[q][g], bh, bm, bl);
+        p[g] = mfma6(p[g], ah, am, al, bh, bm, bl);
       }
       __builtin_amdgcn_sched_barrier(0);  // one k-step's fragments live at a time: the register budget is 256
     }
@@ -585,7 +542,7 @@ __device__ __forceinline__ void wmma(const __bf16* a, const WBuf<G>& v, f32x16 (
 template <class G>
 __device__ __forceinline__ void img_put(__bf16* p, int off, float v) {
   __bf16 a, b, c;
-  split1(v, a, b, c);
+  split1_sub(v, a, b, c);
   p[off] = a;
   p[off + 32 * G::RS] = b;
   p[off + 64 * G::RS] = c;

@@ -23,6 +23,7 @@
 //   weight gradient: dw[k][co][row][kw] = sum_pix dy[k][co][pix] img(pix; row, kw)
 //     per (client, image group) partials over that group's pixels, reduced in
 //     group order by reduce_kernel (which also drops the padded slots).
+#include "bf16x6.h"
 #include "conv_common.h"
 
 #include <algorithm>
@@ -33,11 +34,6 @@ namespace stem {
 
 using conv::FastDiv;
 using conv::udiv;
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-using rsrc_t = __amdgpu_buffer_rsrc_t;
 
 constexpr int NI = 4;        // images per workgroup
 constexpr int THREADS = 256;
@@ -53,38 +49,6 @@ struct Args {
   int64_t sxk, sxc, sxb, syk, syc;
   FastDiv d_hw, d_w, d_nhw, d_howo, d_wo;
 };
-
-__device__ __forceinline__ void split3(const float (&v)[8], bf16x8& hi, bf16x8& mid, bf16x8& lo) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const __bf16 a = (__bf16)v[j];
-    const float r1 = v[j] - (float)a;
-    const __bf16 b = (__bf16)r1;
-    hi[j] = a;
-    mid[j] = b;
-    lo[j] = (__bf16)(r1 - (float)b);
-  }
-}
-
-__device__ __forceinline__ f32x16 mfma6(const bf16x8& ah, const bf16x8& am, const bf16x8& al, const bf16x8& bh,
-                                        const bf16x8& bm, const bf16x8& bl, f32x16 c) {
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bm, c, 0, 0, 0);  // small terms first
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bm, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bh, c, 0, 0, 0);
-  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh, c, 0, 0, 0);
-  return c;
-}
-
-__device__ __forceinline__ rsrc_t make_rsrc(const float* p, int64_t nfloats) {
-  const uint64_t a = reinterpret_cast<uint64_t>(p);
-  const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)a);
-  const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(a >> 32));
-  const int bytes = __builtin_amdgcn_readfirstlane((int)(nfloats * 4));
-  void* b = reinterpret_cast<void*>(((uint64_t)hi << 32) | lo);
-  return __builtin_amdgcn_make_buffer_rsrc(b, (short)0, bytes, 0x00020000);
-}
 
 // img[bl][ci][Hp][Wp] <- the NI images b0 .. b0+NI-1 of client x, zero-padded
 // (x is [Cin][B][H][W]: for a fixed channel the NI images are one contiguous
@@ -142,12 +106,12 @@ __global__ __launch_bounds__(THREADS, 2) void fwd_kernel(const float* __restrict
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const bool ok = co < a.Cout && row < a.CK && j < a.KW;
-        const unsigned off = ok ? (unsigned)((co * RW + row * a.KW + j) * 4) : 0x80000000u;
+        const unsigned off = ok ? (unsigned)((co * RW + row * a.KW + j) * 4) : SENT;
         v[s][j] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rw, off, 0, 0));
       }
     }
 #pragma unroll
-    for (int s = 0; s < NKS; ++s) split3(v[s], wh[s], wm[s], wl[s]);
+    for (int s = 0; s < NKS; ++s) split3_sub(v[s], wh[s], wm[s], wl[s]);
   }
   // LDS offset of (ci, kh) of this lane half's row, per k-step (rows past Cin*KH: any real row)
   int cb[NKS];
@@ -180,8 +144,8 @@ __global__ __launch_bounds__(THREADS, 2) void fwd_kernel(const float* __restrict
         v[2 * q + 1] = f.y;
       }
       bf16x8 bh, bm, bl8;
-      split3(v, bh, bm, bl8);
-      acc = mfma6(wh[s], wm[s], wl[s], bh, bm, bl8, acc);
+      split3_sub(v, bh, bm, bl8);
+      acc = mfma6(acc, wh[s], wm[s], wl[s], bh, bm, bl8);
     }
     // C/D map: col = lane & 31 (pixel), row = (e & 3) + 8 (e >> 2) + 4 h (output channel)
 #pragma unroll
@@ -214,7 +178,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgt_kernel(const float* __restrict
   const bool cok = co < a.Cout;
   const unsigned arow = (unsigned)((min(co, a.Cout - 1) * a.syc + (int64_t)b0 * HoWo) * 4);
   auto load_a = [&](int ks, float (&v)[8]) {
-    const unsigned off = cok ? arow + (unsigned)((16 * ks + 8 * h) * 4) : 0x80000000u;
+    const unsigned off = cok ? arow + (unsigned)((16 * ks + 8 * h) * 4) : SENT;
     const f32x4 p = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rdy, off, 0, 0));
     const f32x4 q = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rdy, off + 16u, 0, 0));
 #pragma unroll
@@ -242,7 +206,7 @@ __global__ __launch_bounds__(THREADS, 2) void wgt_kernel(const float* __restrict
     const int oh = (int)udiv((uint32_t)q, a.d_wo), ow = q - oh * a.Wo;
     const int pb = bl * a.IMG + oh * S * a.Wp + ow * S;
     bf16x8 ah, am, al;
-    split3(av, ah, am, al);
+    split3_sub(av, ah, am, al);
 #pragma unroll
     for (int t = 0; t < NTW; ++t) {
       const float* src = img + pb + lb[t];
@@ -250,8 +214,8 @@ __global__ __launch_bounds__(THREADS, 2) void wgt_kernel(const float* __restrict
 #pragma unroll
       for (int j = 0; j < 8; ++j) v[j] = src[j * S];
       bf16x8 bh, bm, bl8;
-      split3(v, bh, bm, bl8);
-      acc[t] = mfma6(ah, am, al, bh, bm, bl8, acc[t]);
+      split3_sub(v, bh, bm, bl8);
+      acc[t] = mfma6(acc[t], ah, am, al, bh, bm, bl8);
     }
   }
   const int cop = 64 * gridDim.z;

@@ -1,56 +1,42 @@
-// Bit-compares the bf16x3 split of the conv/GEMM kernels (round-to-nearest
-// hi, mid, lo) done two ways: bf16 -> fp32 expansion + subtraction, and the
-// v_dot2_f32_bf16 residual (r = v - hi in one instruction).  Random fp32 bit
-// patterns over every finite exponent, plus signed zeros and denormals.
-#include <hip/hip_runtime.h>
-#include <cstdio>
-#include <cstdint>
-#include <vector>
-#include <random>
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+// Bit-compares the two shipped forms of the bf16x3 split (csrc/bf16x6.h; round-
+// to-nearest hi, mid, lo): split3_sub, bf16 -> fp32 expansion + subtraction (the
+// GRU, the stem), and split3_dot2, the v_dot2_f32_bf16 residual (the conv
+// engine).  Random fp32 bit patterns over every finite exponent, plus signed
+// zeros and denormals.
+// build: hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off tools/hip/split_check.hip -o tools/hip/split_check
+#include "../../multimodal-fl-security_amd/csrc/bf16x6.h"
 
+#include <cmath>
+#include <cstdio>
+#include <random>
+#include <vector>
+
+// one thread: 8 consecutive values, the unit both forms take
 __global__ void split_both(const float* __restrict__ x, int n, unsigned* __restrict__ bad) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (2 * i + 1 >= n) return;
-  const float v0 = x[2 * i], v1 = x[2 * i + 1];
-  // reference form
-  const __bf16 a0 = (__bf16)v0, a1 = (__bf16)v1;
-  const float r0 = v0 - (float)a0, r1 = v1 - (float)a1;
-  const __bf16 b0 = (__bf16)r0, b1 = (__bf16)r1;
-  const __bf16 c0 = (__bf16)(r0 - (float)b0), c1 = (__bf16)(r1 - (float)b1);
-  // dot2 form
-  // (-1, 0) and (0, -1) as opaque SGPRs: hipcc encodes a (-1, 0) constant as the
-  // inline constant -1.0, which the hardware reads as fp32 bits (0, -1)
-  unsigned klo, khi;
-  asm volatile("s_mov_b32 %0, 0xbf80" : "=s"(klo));
-  asm volatile("s_mov_b32 %0, 0xbf800000" : "=s"(khi));
-  const bf16x2 nlo = __builtin_bit_cast(bf16x2, klo), nhi = __builtin_bit_cast(bf16x2, khi);
-  const bf16x2 h = {(__bf16)v0, (__bf16)v1};
-  const float s0 = __builtin_amdgcn_fdot2_f32_bf16(h, nlo, v0, false);
-  const float s1 = __builtin_amdgcn_fdot2_f32_bf16(h, nhi, v1, false);
-  const bf16x2 m = {(__bf16)s0, (__bf16)s1};
-  const float t0 = __builtin_amdgcn_fdot2_f32_bf16(m, nlo, s0, false);
-  const float t1 = __builtin_amdgcn_fdot2_f32_bf16(m, nhi, s1, false);
-  const __bf16 l0 = (__bf16)t0, l1 = (__bf16)t1;
+  if (8 * i + 7 >= n) return;
+  float v[8];
+  for (int e = 0; e < 8; ++e) v[e] = x[8 * i + e];
+  flr::bf16x8 sh, sm, sl, dh, dm, dl;
+  flr::split3_sub(v, sh, sm, sl);
+  flr::split3_dot2(v, dh, dm, dl);
   auto u = [](__bf16 z) { return (unsigned)__builtin_bit_cast(unsigned short, z); };
-  unsigned e = 0;
-  e |= (u(a0) != u(h[0])) | (u(a1) != u(h[1]));
-  e |= ((u(b0) != u(m[0])) | (u(b1) != u(m[1]))) << 1;
-  e |= ((u(c0) != u(l0)) | (u(c1) != u(l1))) << 2;
-  if (e) {
-    atomicOr(bad, e);
+  // a mismatch is an error unless the value's residual is denormal (|v| < 2^-100),
+  // its bf16 rounding overflows (|v| > 0x1.fep127, where both forms give inf/nan), or
+  // the rounding of its dot2 pair partner does (element e ^ 1, the other half of the
+  // same v_dot2 operand): there inf * 0 makes the dot2 residual NaN while the
+  // subtraction form stays finite (bf16x6.h).  The count without the last exemption
+  // is printed too.
+  auto plain = [](float f) { return fabsf(f) >= 0x1p-100f && fabsf(f) <= 0x1.fep127f; };
+  for (int e = 0; e < 8; ++e) {
+    const unsigned m = (u(sh[e]) != u(dh[e])) | ((u(sm[e]) != u(dm[e])) << 1) | ((u(sl[e]) != u(dl[e])) << 2);
+    if (!m) continue;
+    atomicOr(bad, m);
     const unsigned slot = atomicAdd(bad + 1, 1u);
-    if (slot < 8) {  // the first mismatching pairs' magnitudes
-      bad[2 + 2 * slot] = __builtin_bit_cast(unsigned, v0);
-      bad[3 + 2 * slot] = __builtin_bit_cast(unsigned, v1);
-    }
+    if (slot < 16) bad[2 + slot] = __builtin_bit_cast(unsigned, v[e]);  // the first mismatching values
+    if (plain(v[e])) atomicAdd(bad + 18, 1u);
+    if (plain(v[e]) && fabsf(v[e ^ 1]) <= 0x1.fep127f) atomicAdd(bad + 19, 1u);
   }
-  // a mismatch is an error unless a value's residual is denormal (|v| < 2^-100)
-  // or its bf16 rounding overflows (|v| > 0x1.fep127, where both forms give inf/nan)
-  auto plain = [](float v) { return fabsf(v) >= 0x1p-100f && fabsf(v) <= 0x1.fep127f; };
-  const bool e0 = (u(a0) != u(h[0])) | (u(b0) != u(m[0])) | (u(c0) != u(l0));
-  const bool e1 = (u(a1) != u(h[1])) | (u(b1) != u(m[1])) | (u(c1) != u(l1));
-  if ((e0 && plain(v0)) || (e1 && plain(v1))) atomicAdd(bad + 18, 1u);
 }
 
 int main() {
@@ -63,16 +49,16 @@ int main() {
     if (i % 97 == 0) b &= 0x807fffffu;                        // denormals and signed zeros
     h[i] = __builtin_bit_cast(float, b);
   }
-  float* d; unsigned* bad;
-  if (hipMalloc(&d, n * 4) || hipMalloc(&bad, 19 * 4)) return 2;
-  (void)hipMemcpy(d, h.data(), n * 4, hipMemcpyHostToDevice);
-  (void)hipMemset(bad, 0, 19 * 4);
-  split_both<<<(n / 2 + 255) / 256, 256>>>(d, n, bad);
-  unsigned r[19];
-  (void)hipMemcpy(r, bad, 19 * 4, hipMemcpyDeviceToHost);
-  printf("split_check: %d values, mismatch mask %u, mismatching pairs %u, outside the denormal / bf16-overflow ranges %u\n",
-         n, r[0], r[1], r[18]);
-  for (unsigned i = 0; i < 8 && i < r[1]; ++i)
-    printf("  pair %g %g\n", __builtin_bit_cast(float, r[2 + 2 * i]), __builtin_bit_cast(float, r[3 + 2 * i]));
-  return r[18] ? 1 : 0;
+  float* d;
+  unsigned* bad;
+  if (hipMalloc(&d, n * 4) || hipMalloc(&bad, 20 * 4)) return 2;
+  if (hipMemcpy(d, h.data(), n * 4, hipMemcpyHostToDevice) || hipMemset(bad, 0, 20 * 4)) return 2;
+  split_both<<<(n / 8 + 255) / 256, 256>>>(d, n, bad);
+  unsigned r[20];
+  if (hipMemcpy(r, bad, 20 * 4, hipMemcpyDeviceToHost)) return 2;
+  printf("split_check: %d values, split3_sub vs split3_dot2: mismatch mask %u, mismatching values %u, outside the "
+         "denormal / own-overflow ranges %u, of those with a pair partner that does not overflow (errors) %u\n",
+         n, r[0], r[1], r[18], r[19]);
+  for (unsigned i = 0; i < 16 && i < r[1]; ++i) printf("  value %g\n", __builtin_bit_cast(float, r[2 + i]));
+  return r[19] ? 1 : 0;
 }
