@@ -979,6 +979,121 @@ int flr_rlr_fedavg(const float* X, int64_t K, int64_t P, int64_t ldx,
                    float* out, int32_t* votes_out /* optional */,
                    int64_t* flipped /* optional */, void* stream);
 
+/* ---- SparseFed (Panda et al., AISTATS 2022) and the magnitude top-k ---------
+ * "SparseFed: Mitigating Model Poisoning Attacks in Federated Learning with
+ * Sparsification", Algorithm 1: the clients' updates are clipped to a norm L and
+ * averaged, the average is added to a server-side error memory W, only the k
+ * largest-magnitude coordinates of W are applied to the model, and the rest stay
+ * in W for later rounds.  No reference counterpart.  With g the round's global
+ * model, x_i row i of X, rho the momentum, W and U (the momentum's memory) device
+ * fp32 [P] state of the caller, +0 at first use.  Every fp32 operation is rounded
+ * on its own (no FMA).  Calls: flr_row_norms (e_i = ||x_i - g||, fp64),
+ * flr_sparsefed_weights, flr_sparsefed_accumulate, flr_topk_abs_select,
+ * flr_sparsefed_apply, each enqueued on the stream: nothing is allocated or
+ * copied to the host inside them, so they can be captured into a graph; nothing
+ * is written on an error.  tests/sparsefed_ref.py restates the arithmetic.
+ *
+ * flr_sparsefed_weights: one workgroup, fp64, only + - * / and comparisons.
+ *   Row i is bad when e_i (norms[i]) is not finite: beta_i = 0.f exactly (the
+ *     later passes do not read it: flr_rows_combine_from's convention) and bit 1
+ *     of flags.
+ *   n = the number of good rows.  n == 0: every beta 0, L = 0, bit 0 of flags.
+ *   L = clip_norm when it is > 0, else (clip_norm == 0) the lower median of the
+ *     good rows' e, sorted[(n - 1) / 2].  The adaptive default is this library's
+ *     choice, as FLAME's bound is; the paper's L is a tuned constant.
+ *   gamma_i = L / e_i when e_i > L, else 1;  beta_i = (float)(gamma_i / n).
+ *   norms: device fp64 [K]; beta: device fp32 [K]; optional (NULL: not written)
+ *   stats fp64 [3]: L, n, the number of rows with e_i > L; flags int32 [1].
+ *   FLR_ERR_ARG: null norms or beta; K < 1; clip_norm negative, NaN or infinite.
+ *   FLR_ERR_UNSUPPORTED: K > 4096.
+ *
+ * flr_sparsefed_accumulate: the K x P pass.  Per coordinate p:
+ *     a = +0;  for i in 0..K-1:  if beta_i != 0:  a = a + (x_i[p] - g[p]) * beta_i
+ *   (flr_rows_combine_from's accumulator without the final + c; a row with beta_i
+ *   == 0 is not read)
+ *     rho != 0:  u = rho * U[p] + a   (the product, then the sum);  U[p] = u
+ *     rho == 0:  u = a; U is not touched and may be NULL
+ *     w = W[p] + u
+ *     w not finite:  W[p] = +0, with rho != 0 also U[p] = +0, and the coordinate
+ *                    counts into dropped;  else W[p] = w
+ *   and the key (below) of the stored W[p] is counted into hist, the level-1
+ *   histogram flr_topk_abs_select takes.  hist: optional device uint32 [2048];
+ *   dropped: optional device int64 [1]; the call zeroes both on the stream first.
+ *   Each workgroup counts into a private LDS histogram and flushes it with one
+ *   integer atomicAdd per non-empty bin; dropped is one atomicAdd per workgroup:
+ *   integer sums, the same from run to run.  One lane owns one float4 of
+ *   coordinates, or one coordinate when a pointer is not 16-byte aligned or ldx % 4
+ *   != 0: the same bits.  Columns [P, ldx) are never touched; X, g and beta are
+ *   only read.  Bytes moved: (rows with beta != 0) * P * 4 + 12 * P (+ 8 * P with
+ *   the momentum).
+ *   FLR_ERR_ARG: null X, g, beta or W; K < 1; P < 0; ldx < P; rho outside [0, 1)
+ *   or NaN; rho != 0 with a null U; W, U and g not distinct.
+ *   FLR_ERR_UNSUPPORTED: K > 4096; P >= 2^32 (the counts are 32-bit).
+ *   P == 0: FLR_OK, nothing enqueued.
+ *
+ * flr_topk_abs_select: the exact, deterministic magnitude top-k of any fp32
+ * vector v [P], 1 <= k <= P.
+ *     key(v) = bits(v) & 0x7fffffff when that is below 0x7f800000, else 0
+ *   a NaN or an inf ranks with zero and sets bit 0 of the flags.  A radix select
+ *   on three digits of the 31-bit key, d1 = key >> 20 (2048 bins), d2 = (key >> 9)
+ *   & 0x7ff (2048 bins), d3 = key & 0x1ff (512 bins): per level a histogram pass
+ *   over v that counts the keys matching the digits found so far, and a
+ *   one-workgroup scan from the top bin down to the bin where the running count
+ *   reaches the remaining k.  hist1: optional device uint32 [2048], the level-1
+ *   histogram of v's keys (flr_sparsefed_accumulate's): level 1's pass over v is
+ *   then skipped; the result is the same.  It must be the histogram of this v as
+ *   it stands: with another one the scans may find no bin, and sel is then left
+ *   unwritten or names a threshold that is not v's.  Then a count pass gives each chunk's
+ *   number of keys == T (a chunk: 1024 adjacent coordinates; the chunk map is a
+ *   function of P alone) and a one-workgroup exclusive scan over the chunks leaves
+ *   the ties' prefix in the workspace, for flr_topk_abs_mask / flr_sparsefed_apply.
+ *   sel: device uint32 [4]:  T, the key of the k-th largest;  n_gt, the number
+ *   of keys > T;  r = k - n_gt, 1 <= r <= n_eq (the number of keys == T);  the
+ *   flags.  Coordinate p is selected when key > T, or key == T and fewer than r
+ *   coordinates q < p have key == T: the lowest indices win, as in a stable
+ *   descending sort of the keys.  k == P selects everything.  No kernel waits on
+ *   another workgroup: every dependency is a kernel boundary on the stream.
+ *   workspace: flr_topk_abs_workspace(P) bytes, 256-byte aligned (0 for a
+ *   rejected P): the histograms and the per-chunk tie counts; a later mask or
+ *   apply call reads it, so it must stay untouched between the calls.  Bytes
+ *   moved: 16 * P (12 * P with hist1), from the Infinity Cache when v fits.
+ *   FLR_ERR_ARG: null v or sel; P < 0; k outside [1, P].  FLR_ERR_UNSUPPORTED:
+ *   P >= 2^32.  FLR_ERR_WORKSPACE.  P == 0: FLR_OK, nothing enqueued.
+ *
+ * flr_topk_abs_mask: mask[p] = 1 for a selected coordinate, else 0, from sel and
+ * the workspace of flr_topk_abs_select on the same v.  mask: device uint8 [P].
+ * The in-chunk tie rank is a wave ballot prefix, then the waves' counts through
+ * LDS.  Bytes moved: 5 * P.
+ *
+ * flr_sparsefed_apply: with sel and the workspace of flr_topk_abs_select on W,
+ *     selected:      out[p] = g[p] + W[p];  W[p] = +0;  U[p] = +0 when U is given
+ *                    (FetchSGD's momentum masking)
+ *     not selected:  out[p] = g[p], the same bits
+ *   out must not be g or W; U optional; mask: optional device uint8 [P], as
+ *   flr_topk_abs_mask's.  Bytes moved: 12 * P (+ P with mask) and 4 * k per state
+ *   vector.
+ *   FLR_ERR_ARG (both): a null required pointer; P < 0; out == g, out == W, or g,
+ *   W, U not distinct.  FLR_ERR_UNSUPPORTED: P >= 2^32.  FLR_ERR_WORKSPACE.
+ *   P == 0: FLR_OK, nothing enqueued. */
+int flr_sparsefed_weights(const double* norms, int64_t K, double clip_norm /* 0: the median */,
+                          float* beta, double* stats /* optional: L, n, clipped */,
+                          int32_t* flags /* optional */, void* stream);
+int flr_sparsefed_accumulate(const float* X, int64_t K, int64_t P, int64_t ldx, const float* g,
+                             const float* beta /* device [K] */, float rho, float* W,
+                             float* U /* NULL allowed when rho == 0 */,
+                             uint32_t* hist /* optional, device [2048] */,
+                             int64_t* dropped /* optional */, void* stream);
+size_t flr_topk_abs_workspace(int64_t P);
+int flr_topk_abs_select(const float* v, int64_t P, int64_t k,
+                        const uint32_t* hist1 /* optional, device [2048] */,
+                        uint32_t* sel /* device [4] */, void* workspace, size_t workspace_bytes,
+                        void* stream);
+int flr_topk_abs_mask(const float* v, int64_t P, const uint32_t* sel, const void* workspace,
+                      size_t workspace_bytes, uint8_t* mask, void* stream);
+int flr_sparsefed_apply(const float* g, float* W, float* U /* optional */, int64_t P,
+                        const uint32_t* sel, const void* workspace, size_t workspace_bytes,
+                        float* out, uint8_t* mask /* optional */, void* stream);
+
 /* ---- a6 + a7: fused gradient clip + SGD-momentum step -----------------
  * Replaces, for every client row at once, clip_grad_norm_(params, max_norm)
  * + torch.optim.SGD(lr, momentum, weight_decay).step()

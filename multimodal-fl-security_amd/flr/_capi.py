@@ -114,6 +114,14 @@ SIGNATURES = {
                              _c_void_p]),
     "flr_rlr_fedavg": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, _i64, ctypes.c_float, _c_void_p,
                               _c_void_p, _c_void_p, _c_void_p]),
+    "flr_sparsefed_weights": (_int, [_c_void_p, _i64, ctypes.c_double, _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "flr_sparsefed_accumulate": (_int, [_c_void_p, _i64, _i64, _i64, _c_void_p, _c_void_p, ctypes.c_float, _c_void_p,
+                                        _c_void_p, _c_void_p, _c_void_p, _c_void_p]),
+    "flr_topk_abs_workspace": (_size_t, [_i64]),
+    "flr_topk_abs_select": (_int, [_c_void_p, _i64, _i64, _c_void_p, _c_void_p, _c_void_p, _size_t, _c_void_p]),
+    "flr_topk_abs_mask": (_int, [_c_void_p, _i64, _c_void_p, _c_void_p, _size_t, _c_void_p, _c_void_p]),
+    "flr_sparsefed_apply": (_int, [_c_void_p, _c_void_p, _c_void_p, _i64, _c_void_p, _c_void_p, _size_t, _c_void_p,
+                                   _c_void_p, _c_void_p]),
     "flr_clip_sgd_workspace": (_size_t, [_i64]),
     "flr_clip_sgd_step": (_int, [_c_void_p, _c_void_p, _c_void_p, _i64, _i64, _i64, ctypes.c_float, ctypes.c_float,
                                  ctypes.c_float, ctypes.c_float, _int, _c_void_p, _c_void_p, _size_t, _c_void_p]),

@@ -14,13 +14,14 @@ from .foolsgold import FoolsGoldDefense
 from .geometric_median import GeometricMedianDefense
 from .norm_based import DPSGDDefense, GradientClippingDefense, NormBoundingDefense
 from .robust_lr import RobustLRDefense
+from .sparsefed import SparseFedDefense
 from .trimmed_mean import MedianDefense, TrimmedMeanDefense
 
 __all__ = [
     "BaseDefense", "CenteredDefense", "NoDefense", "KrumDefense", "MultiKrumDefense", "KrumTrimmedMeanDefense", "BulyanDefense",
     "TrimmedMeanDefense", "MedianDefense", "GeometricMedianDefense",
     "GradientClippingDefense", "NormBoundingDefense", "DPSGDDefense", "FLTrustDefense", "CenteredClippingDefense",
-    "DnCDefense", "FoolsGoldDefense", "RobustLRDefense", "FlameDefense",
+    "DnCDefense", "FoolsGoldDefense", "RobustLRDefense", "FlameDefense", "SparseFedDefense",
     "get_defense", "defense_names",
 ]
 
@@ -55,6 +56,8 @@ _DEFENSES = {
 _LATER_DEFENSES = {
     # FLAME (USENIX Security 2022): the majority cluster of the cosine distances, median clipping, Gaussian noise
     "flame": FlameDefense,
+    # SparseFed (AISTATS 2022): clipped mean into a server-side error memory, only its top-k coordinates applied
+    "sparsefed": SparseFedDefense,
 }
 
 

@@ -808,6 +808,155 @@ def rlr_fedavg(X: torch.Tensor, num_examples, g: torch.Tensor, theta: int, eta: 
     return (out, votes, flipped) if diagnostics else out
 
 
+SPARSEFED_MAX_CLIENTS = 4096  # flr_sparsefed_weights' and flr_sparsefed_accumulate's limit
+TOPK_BINS = 2048              # the level-1 histogram of flr_topk_abs_select
+# The select's scratch, kept per (device, stream) like the reference distances': a
+# mask or apply call reads what the last select on that device and stream left.
+_TOPK_WS: Dict[Tuple[int, int], torch.Tensor] = {}
+
+
+def _topk_workspace(P: int, device, stream: int) -> Tuple[int, int]:
+    nbytes = int(_capi.lib().flr_topk_abs_workspace(P))
+    index = torch.device(device).index
+    key = (torch.cuda.current_device() if index is None else index, stream)
+    ws = _TOPK_WS.get(key)
+    if ws is None or ws.numel() < nbytes + 256:
+        _TOPK_WS.pop(key, None)
+        ws = torch.empty(max(nbytes, 256) + 256, dtype=torch.uint8, device=device)
+        _TOPK_WS[key] = ws
+    return ws.data_ptr() + (-ws.data_ptr()) % 256, nbytes
+
+
+def _check_topk_vector(v, name: str) -> int:
+    if not isinstance(v, torch.Tensor) or not v.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA/HIP tensor (the engine has no CPU path)")
+    if v.dtype != torch.float32 or v.dim() != 1 or not v.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous float32 vector (got {v.dtype}, shape {tuple(v.shape)})")
+    if v.numel() >= 2 ** 32:
+        raise ValueError(f"{name} holds {v.numel()} coordinates, the select's counts are 32-bit")
+    return v.numel()
+
+
+def sparsefed_weights(norms: torch.Tensor, clip_norm: Optional[float] = None, diagnostics: bool = False):
+    """SparseFed's clipped weights from the clients' update norms
+    (flr_sparsefed_weights; the arithmetic in include/flr.h): with n the rows
+    whose norm is finite and L = clip_norm, or for None the lower median of those
+    rows' norms, beta_i = float32(min(1, L / e_i) / n), exactly 0 for a row with a
+    non-finite norm.  norms: float64 [K].  Returns beta float32 [K], or with
+    diagnostics (beta, stats float64 [3]: L, n, the rows clipped, flags int32 [1]:
+    bit 0 no good row, bit 1 a bad row) as device tensors."""
+    if not isinstance(norms, torch.Tensor) or not norms.is_cuda:
+        raise RuntimeError("norms must be a CUDA/HIP tensor (the engine has no CPU path)")
+    K = norms.numel()
+    _check_vector(norms, K, norms.device, "norms", torch.float64)
+    if K < 1:
+        raise ValueError("sparsefed_weights needs K >= 1")
+    if K > SPARSEFED_MAX_CLIENTS:
+        raise ValueError(f"sparsefed_weights handles at most {SPARSEFED_MAX_CLIENTS} clients, got {K}")
+    clip = 0.0
+    if clip_norm is not None:
+        clip = float(clip_norm)
+        if not 0.0 < clip < float("inf"):
+            raise ValueError(f"clip_norm must be None or a finite number > 0, got {clip_norm!r}")
+    beta = torch.empty(K, dtype=torch.float32, device=norms.device)
+    stats = flags = None
+    if diagnostics:
+        stats = torch.empty(3, dtype=torch.float64, device=norms.device)
+        flags = torch.empty(1, dtype=torch.int32, device=norms.device)
+    _capi.call("flr_sparsefed_weights", norms.data_ptr(), K, clip, beta.data_ptr(), _ptr(stats), _ptr(flags),
+               _stream(norms))
+    return (beta, stats, flags) if diagnostics else beta
+
+
+def sparsefed_accumulate_(X: torch.Tensor, g: torch.Tensor, beta: torch.Tensor, W: torch.Tensor,
+                          U: Optional[torch.Tensor] = None, rho: float = 0.0, diagnostics: bool = False):
+    """W += [rho * U +] sum_i (X_i - g) * beta_i in place (flr_sparsefed_accumulate):
+    fp32, the rows in ascending order, every op separately rounded; rows with
+    beta_i == 0 are not read; with rho != 0, U <- rho * U + the sum first.  A
+    coordinate whose new W is not finite is set to +0 (U too) and counted.  W, U:
+    float32 [P] on X's device (U only with rho != 0).  Returns W, or with
+    diagnostics (W, hist uint32-as-int32 [2048]: the level-1 histogram of W's
+    keys for topk_abs_select, dropped int64 [1]) as device tensors."""
+    K, P, ldx = _check_matrix(X)
+    if K < 1:
+        raise ValueError("sparsefed_accumulate_ needs K >= 1")
+    if K > SPARSEFED_MAX_CLIENTS:
+        raise ValueError(f"sparsefed_accumulate_ handles at most {SPARSEFED_MAX_CLIENTS} rows, got {K}")
+    rho = float(rho)
+    if not 0.0 <= rho < 1.0:
+        raise ValueError(f"rho must be in [0, 1), got {rho}")
+    _check_vector(g, P, X.device, "g")
+    _check_vector(beta, K, X.device, "beta")
+    _check_vector(W, P, X.device, "W")
+    if rho != 0.0:
+        _check_vector(U, P, X.device, "U")
+    hist = dropped = None
+    if diagnostics:
+        hist = torch.empty(TOPK_BINS, dtype=torch.int32, device=X.device)
+        dropped = torch.empty(1, dtype=torch.int64, device=X.device)
+        if P == 0:
+            hist.zero_()
+            dropped.zero_()
+    if P:  # an empty tensor has no address
+        _capi.call("flr_sparsefed_accumulate", X.data_ptr(), K, P, ldx, g.data_ptr(), beta.data_ptr(), rho,
+                   W.data_ptr(), _ptr(U) if rho != 0.0 else None, _ptr(hist), _ptr(dropped), _stream(X))
+    return (W, hist, dropped) if diagnostics else W
+
+
+def topk_abs_select(v: torch.Tensor, k: int, hist: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The exact magnitude top-k of v (flr_topk_abs_select): a three-digit radix
+    select on key = bits & 0x7fffffff (a NaN or an inf ranks with zero).  Returns
+    sel, int32 [4] on the device holding the uint32 words T (the k-th largest
+    key), n_gt (the keys above it), r (how many of the keys == T are selected: the
+    lowest indices) and the flags (bit 0: v holds a NaN or an inf).  hist: the
+    level-1 histogram of v's keys when sparsefed_accumulate_ counted it.  The
+    scratch topk_abs_mask / sparsefed_apply_ read is kept per device and stream:
+    call them before the next select there."""
+    P = _check_topk_vector(v, "v")
+    k = int(k)
+    if not 1 <= k <= P:
+        raise ValueError(f"k must be in [1, {P}], got {k}")
+    if hist is not None:
+        _check_vector(hist, TOPK_BINS, v.device, "hist", torch.int32)
+    sel = torch.empty(4, dtype=torch.int32, device=v.device)
+    wp, nbytes = _topk_workspace(P, v.device, _stream(v))
+    _capi.call("flr_topk_abs_select", v.data_ptr(), P, k, _ptr(hist), sel.data_ptr(), wp, nbytes, _stream(v))
+    return sel
+
+
+def topk_abs_mask(v: torch.Tensor, sel: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [P]: 1 where topk_abs_select(v, k) selected the coordinate
+    (flr_topk_abs_mask), from sel and that call's scratch."""
+    P = _check_topk_vector(v, "v")
+    if P < 1:
+        raise ValueError("topk_abs_mask needs P >= 1")
+    _check_vector(sel, 4, v.device, "sel", torch.int32)
+    out = _out_vector(out, P, v.device, torch.uint8)
+    wp, nbytes = _topk_workspace(P, v.device, _stream(v))
+    _capi.call("flr_topk_abs_mask", v.data_ptr(), P, sel.data_ptr(), wp, nbytes, out.data_ptr(), _stream(v))
+    return out
+
+
+def sparsefed_apply_(g: torch.Tensor, W: torch.Tensor, sel: torch.Tensor, U: Optional[torch.Tensor] = None,
+                     out: Optional[torch.Tensor] = None, mask: bool = False):
+    """out = g + W on the coordinates topk_abs_select(W, k) selected, where W (and
+    U when given) become +0; g's bits elsewhere (flr_sparsefed_apply).  out must
+    not be g or W.  Returns out, or with mask (out, mask uint8 [P])."""
+    P = _check_topk_vector(W, "W")
+    if P < 1:
+        raise ValueError("sparsefed_apply_ needs P >= 1")
+    _check_vector(g, P, W.device, "g")
+    if U is not None:
+        _check_vector(U, P, W.device, "U")
+    _check_vector(sel, 4, W.device, "sel", torch.int32)
+    out = _out_vector(out, P, W.device)
+    m = torch.empty(P, dtype=torch.uint8, device=W.device) if mask else None
+    wp, nbytes = _topk_workspace(P, W.device, _stream(W))
+    _capi.call("flr_sparsefed_apply", g.data_ptr(), W.data_ptr(), _ptr(U), P, sel.data_ptr(), wp, nbytes,
+               out.data_ptr(), _ptr(m), _stream(W))
+    return (out, m) if mask else out
+
+
 def row_norms(X: torch.Tensor, center: Optional[torch.Tensor] = None, kind: str = "l2") -> torch.Tensor:
     """float64 [K]: ||X_i - center|| per row (l2 or linf); fp32 differences,
     fp64 accumulation in a fixed order (differential_privacy.py:223-236,
@@ -889,8 +1038,9 @@ def _ref_workspace(K: int, P: int, device, stream: int) -> Tuple[int, int]:
 
 
 def release_workspaces() -> None:
-    """Drop the cached reference-exact workspaces (their HBM returns to torch's allocator)."""
+    """Drop the cached reference-exact and top-k workspaces (their HBM returns to torch's allocator)."""
     _REF_WS.clear()
+    _TOPK_WS.clear()
 
 
 def pairwise_l2_reference_sharded(cs, tap_blocks=None) -> torch.Tensor:
